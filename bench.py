@@ -3,7 +3,7 @@
 
 Workloads (BASELINE.json configs; `--workload`; default: C3 = the headline, at every N -- one alignment per GPU per step, weak
 scaling, so that the lines of a 1 / 2 / 4 / 8 run hold the same per-GPU work; BASELINE config 5, the batch of 64 sharded over the
-ranks, is timed behind it and rides in the same line as `c5_batch`):
+ranks, is timed behind it under `--full` and rides in the same line as `c5_batch`):
   C3  AutomaticTrimmer('automated1') on a synthetic 2 000 x 10 000 protein MSA (seed 1003 + rank: all eight golden)
   C2  ManualTrimmer(gap_threshold=0.5, similarity_threshold=0.5) on 500 x 2 000 (seed 1002 + rank)
   C4  RepresentativeTrimmer(identity_threshold=0.5) on 5 000 x 5 000 (seed 1004 + rank)
@@ -12,16 +12,24 @@ ranks, is timed behind it and rides in the same line as `c5_batch`):
   REF the reference's own protocol (/root/reference/bench/bench.py:48-57,94-101): 3583 x 7287, the four statistic ->
       trimmer mappings, whole `trimmer.trim(alignment)` calls through the public API, median of 3.
 One "step" = one pass of the whole path over the workload's input, FROM HOST ROWS: pack + H2D, kernels, D2H, host
-selection logic -- SURVEY 8(d)'s metric, `value` / `ms_per_step`.  For C2-C4 the same steps with the residue bytes
-already resident in HBM (`value_resident`) and through the public API (`AutomaticTrimmer(...).trim(Alignment)` ->
-`TrimmedAlignment`: `value_public_api`) are timed right after.
+selection logic -- SURVEY 8(d)'s metric, `value` / `ms_per_step`.
+
+A plain run sets up, warms up (`--warmup W` steps), times exactly `--steps K` steps and prints the line.  Everything
+else is measured only under `--full`: for C2-C4 the same steps with the residue bytes already resident in HBM
+(`value_resident`), through the public API (`AutomaticTrimmer(...).trim(Alignment)` -> `TrimmedAlignment`:
+`value_public_api`), from page-locked rows and cold, four more timed regions, per-kernel times and `roofline` (dominant
+kernel, HIP-event timed on the context's own stream, those events inside the timed region), the similarity kernel's
+clock, config 5 behind C3 (`c5_batch`), the one-GPU reference of a multi-rank C5 run and, at N = 1, `cpu_baseline`
+(the CPU oracle, scalar and AVX2 flavours, on a bounded sample of the same workload).
+
+`--dump-outputs DIR` writes what the last timed step returned (the kept-column and kept-sequence masks as float32, the
+trim's scalar results as float64; for C5 the masks of the whole batch) to DIR/<name>.npy.  The inputs are seeded: runs
+with the same arguments trim the same alignments, so two builds can be compared output for output.
 
 `python bench.py --gpus N` starts N rank processes itself when it was not launched by torchrun (RANK unset): the
 parent never touches a GPU, every child is `bench.py` again with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, a
 child that fails makes the parent exit non-zero.  Ranks synchronise with a barrier + device synchronisation on both
-sides of the timed steps, the time is the MAX over ranks, rank 0 prints ONE JSON line with `roofline` (dominant
-kernel, HIP-event timed on the context's own stream) and, at N = 1, `cpu_baseline` (the CPU oracle, scalar and AVX2
-flavours, on a bounded sample of the same workload).
+sides of the timed steps, the time is the MAX over ranks, rank 0 prints ONE JSON line.
 """
 import argparse
 import ctypes
@@ -126,6 +134,27 @@ def algorithmic_bytes(kernel, m, n):
         "cluster": 4 * m * m,
         "overlap": m * n + 4 * m,
     }[kernel]
+
+
+# the scalar results of a trim (TrimInfo) that --dump-outputs writes; not the device time, not the error detail
+TRIM_INFO_FIELDS = ("selected_method", "avg_seq", "max_seq", "gap_cut", "sim_cut", "kept_residues", "kept_sequences", "warnings",
+                    "warn_row")
+
+
+def trim_outputs(keep_res, keep_seq, info=None):
+    """What a trim through the C ABI hands its caller, as the arrays --dump-outputs writes."""
+    out = {"residues_mask": np.asarray(keep_res, dtype=np.float32), "sequences_mask": np.asarray(keep_seq, dtype=np.float32)}
+    if info is not None:
+        out["trim_info"] = np.array([float(getattr(info, f)) for f in TRIM_INFO_FIELDS], dtype=np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 or float64; a few MB at the largest workload, C5)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def launch_ranks(args):
@@ -287,7 +316,7 @@ def run_reference_protocol(args, device):
                 "Similarity": ManualTrimmer(similarity_threshold=0.5, platform="hip"),
                 "Overlap": OverlapTrimmer(60.0, 0.5, platform="hip"),
                 "Identity": RepresentativeTrimmer(identity_threshold=0.5, platform="hip")}
-    results = []
+    results, outputs = [], {}
     for name, tr in trimmers.items():
         tr.trim(ali)
         times = []
@@ -296,6 +325,8 @@ def run_reference_protocol(args, device):
             out = tr.trim(ali)
             times.append(time.perf_counter() - t0)
         sec = float(np.median(times))
+        for k, v in trim_outputs(out.residues_mask, out.sequences_mask).items():
+            outputs[f"{name.lower()}_{k}"] = v
         ctx = _lib.thread_context()
         ctx.prof_enable(True)
         ctx.prof_reset()
@@ -314,6 +345,8 @@ def run_reference_protocol(args, device):
                                                          "hardware": "i7-10710U @ 1.10 GHz, one core",
                                                          "data": "example.014.AA.EggNOG.COG0591.fasta (not in the reference tree)"},
                         "published_avx2_over_this": round(avx2 / sec, 1)})
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if args.out:
         with open(args.out, "w") as f:
             for r in results:
@@ -340,22 +373,31 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: C3 (the headline) at one GPU, C5 (BASELINE config 5, strong scaling) with --gpus N > 1")
     ap.add_argument("--out", default=None, help="REF: also write the four result lines to this file (JSON lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the resident, public-API, page-locked and cold legs, four more "
+                         "timed regions, per-kernel times and roofline, the similarity kernel's clock, config 5 behind C3, the one-GPU "
+                         "reference of a multi-rank C5 run and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-c5-leg", action="store_true",
-                    help="C3 only: do not time BASELINE config 5 (the batch of 64 sharded over the ranks) behind the headline")
+                    help="--full, C3 only: do not time BASELINE config 5 (the batch of 64 sharded over the ranks) behind the headline")
     ap.add_argument("--cpu-sample-cols", type=int, default=10000,
-                    help="columns of the workload's alignment the CPU baseline is timed on (default: all of them at C3: ~7 s per flavour)")
+                    help="--full: columns of the workload's alignment the CPU baseline is timed on (default: all of them at C3: ~7 s per "
+                         "flavour)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing only: every rank on GPU 0, process group over gloo (RCCL needs a GPU per rank) -- runs the whole "
                          "multi-rank code path on a one-GPU box; the line it prints is marked and is not a multi-GPU measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.workload is None:
         # The headline (C3) at every N: one alignment per GPU per step -- `value` of an N-GPU line is then N x the same per-GPU work
         # as the 1-GPU line's (weak scaling: the two divide into an efficiency).  BASELINE config 5 -- the batch of 64 sharded over
-        # the ranks, strong scaling -- is timed behind it at every N and reported in the same line as `c5_batch` (--no-c5-leg skips
-        # it; `--workload C5` makes it the line's `value`).  Until round 6 a run with N > 1 defaulted to C5, so that the lines of a
-        # 1 / 2 / 4 / 8 scaling run held two different workloads.
+        # the ranks, strong scaling -- is timed behind it at every N under --full and reported in the same line as `c5_batch`
+        # (--no-c5-leg skips it; `--workload C5` makes it the line's `value`).  Until round 6 a run with N > 1 defaulted to C5, so
+        # that the lines of a 1 / 2 / 4 / 8 scaling run held two different workloads.
         args.workload = "C3"
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -438,11 +480,11 @@ def main():
         dist.all_reduce(t)
         ranks_seen = int(t.item())
 
-    def run_c5_batch(steps, warmup, with_public_api=True):
+    def run_c5_batch(steps, warmup, with_public_api=True, with_reference=True):
         """BASELINE config 5: the batch of 64 alignments of 1000 x 4000 through `trim_batch`, sharded round-robin over the ranks
         (strong scaling: the batch is the same whatever the number of ranks), from host rows to the masks gathered on rank 0.
         Returns seconds for `steps` steps (max over ranks), the same through the public objects, rank 0's one-GPU reference
-        (world > 1) and the last step's masks."""
+        (world > 1), the columns the last step kept and its masks (rank 0)."""
         from pytrimal_amd.batch import trim_batch
 
         m5, n5, seed5 = WORKLOADS["C5"]
@@ -479,7 +521,7 @@ def main():
         # the same batch on ONE GPU (rank 0 alone, the others wait): the strong-scaling reference, so that a line of an
         # N-GPU run carries the 1-GPU number of the very same workload beside its own
         single_gpu_s = None
-        if world > 1:
+        if world > 1 and with_reference:
             if rank == 0:
                 trim_batch(trimmer, alis, device=None if args.share_gpu else device, threads=4, shard=False, masks_only=True)
                 t0 = time.perf_counter()
@@ -488,25 +530,30 @@ def main():
                 single_gpu_s = (time.perf_counter() - t0) / max(1, min(steps, 5))
             fence()
         kept = int(sum(int(res.sum()) for res, _ in out)) if rank == 0 else None
-        return elapsed, public_api_s, single_gpu_s, kept
+        return elapsed, public_api_s, single_gpu_s, kept, out if rank == 0 else None
 
     c5_leg = None
     if args.workload == "C5":
         units_per_step = C5_BATCH * n  # the whole batch, however many ranks share it: strong scaling
-        elapsed, public_api_s, single_gpu_s, kept = run_c5_batch(args.steps, args.warmup)
-        # kernel times of one alignment of the batch (profiled separately: the batch runs on per-thread contexts)
-        a = synth_msa(m, n, seed + rank)
-        ctx.prof_enable(True)
-        for _ in range(3):
-            ctx.upload(a, ord("X"))
-            _, _, info = ctx.trim(params)
-        ctx.prof_enable(False)
+        elapsed, public_api_s, single_gpu_s, kept, last = run_c5_batch(args.steps, args.warmup, with_public_api=args.full,
+                                                                       with_reference=args.full)
+        if args.dump_outputs and rank == 0:  # (the 64 masks of the batch, in batch order)
+            dump_outputs(args.dump_outputs, trim_outputs(np.stack([r for r, _ in last]), np.stack([s for _, s in last])))
+        if args.full:
+            # kernel times of one alignment of the batch (profiled separately: the batch runs on per-thread contexts)
+            a = synth_msa(m, n, seed + rank)
+            ctx.prof_enable(True)
+            for _ in range(3):
+                ctx.upload(a, ord("X"))
+                _, _, info = ctx.trim(params)
+            ctx.prof_enable(False)
     else:
         a = synth_msa(m, n, seed + rank)
-        ld = (n + 63) // 64 * 64
-        dev = torch.zeros((m, ld), dtype=torch.uint8, device=device)
-        dev[:, :n] = torch.from_numpy(a).to(device)
-        torch.cuda.synchronize()
+        if args.full:  # (the resident leg's copy of the rows in HBM)
+            ld = (n + 63) // 64 * 64
+            dev = torch.zeros((m, ld), dtype=torch.uint8, device=device)
+            dev[:, :n] = torch.from_numpy(a).to(device)
+            torch.cuda.synchronize()
         cdev = "cpu" if args.share_gpu else device  # where the collectives' tensors live
         gathered = [torch.empty(n, dtype=torch.uint8, device=cdev) for _ in range(world)] if rank == 0 else None
         units_per_step = world * n  # one alignment per rank per step: weak scaling
@@ -543,10 +590,11 @@ def main():
             finish(keep_res)
             return keep_res, keep_seq, info
 
-        trimmer_obj = {"C3": lambda: AutomaticTrimmer("automated1", platform="hip"),
-                       "C2": lambda: ManualTrimmer(gap_threshold=0.5, similarity_threshold=0.5, platform="hip"),
-                       "C4": lambda: RepresentativeTrimmer(identity_threshold=0.5, platform="hip")}[args.workload]()
-        ali = Alignment([b"s%d" % i for i in range(m)], [bytes(r) for r in a])
+        if args.full:
+            trimmer_obj = {"C3": lambda: AutomaticTrimmer("automated1", platform="hip"),
+                           "C2": lambda: ManualTrimmer(gap_threshold=0.5, similarity_threshold=0.5, platform="hip"),
+                           "C4": lambda: RepresentativeTrimmer(identity_threshold=0.5, platform="hip")}[args.workload]()
+            ali = Alignment([b"s%d" % i for i in range(m)], [bytes(r) for r in a])
 
         def step_public_api():
             t = trimmer_obj.trim(ali)  # host rows -> TrimmedAlignment, the call a user of the reference makes
@@ -556,88 +604,96 @@ def main():
         for _ in range(args.warmup):
             step_host_rows()
         # THE TIMED REGION (value / ms_per_step): every step starts from the host rows -- SURVEY 8(d).
-        # HIP event pairs around the two pairwise passes -- the dominant kernels, what `roofline` is computed from -- over
-        # the timed region (level 2); the small kernels are timed in a few untimed steps afterwards: seven more event
+        # --full: HIP event pairs around the two pairwise passes -- the dominant kernels, what `roofline` is computed from --
+        # over the timed region (level 2); the small kernels are timed in a few untimed steps afterwards: seven more event
         # pairs per step cost ~10 % of a 0.33 ms step (tools/step_overheads.py)
-        ctx.prof_reset()
-        ctx.prof_enable(2)
+        if args.full:
+            ctx.prof_reset()
+            ctx.prof_enable(2)
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             keep_res, keep_seq, info = step_host_rows()
         fence()
         elapsed = max_over_ranks(time.perf_counter() - t0)
-        ctx.prof_enable(False)
-        # four more regions of the same K steps, same fences: the median of the five says how much of `value` is the box's mood
-        # (a region is 0.07 s at --steps 20, the clock is still ramping in the first)
-        region_ms = [elapsed / args.steps * 1e3]
-        for _ in range(4):
+        kept = int(info.kept_residues)
+        if args.dump_outputs and rank == 0:
+            outputs = trim_outputs(keep_res, keep_seq, info)
+            if dist is not None:  # (every rank's kept-column mask of the last step, as gathered on rank 0)
+                outputs["residues_mask_by_rank"] = np.stack([g.cpu().numpy() for g in gathered]).astype(np.float32)
+            dump_outputs(args.dump_outputs, outputs)
+        if args.full:
+            ctx.prof_enable(False)
+            # four more regions of the same K steps, same fences: the median of the five says how much of `value` is the box's
+            # mood (a region is 0.07 s at --steps 20, the clock is still ramping in the first)
+            region_ms = [elapsed / args.steps * 1e3]
+            for _ in range(4):
+                fence()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step_host_rows()
+                fence()
+                region_ms.append(max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3)
+            for name in ("pairs", "sim"):
+                ms, launches = ctx.prof_get(name)
+                if launches:
+                    kernels[name] = {"ms_avg": ms / launches, "launches": launches}
+            ctx.prof_reset()
+            ctx.prof_enable(True)
+            for _ in range(5):
+                step()
+            fence()
+            ctx.prof_enable(False)
+            # the same steps with the residue bytes resident in HBM (no pack, no H2D)
+            step()
             fence()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                step_host_rows()
+                step()
             fence()
-            region_ms.append(max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3)
-        for name in ("pairs", "sim"):
-            ms, launches = ctx.prof_get(name)
-            if launches:
-                kernels[name] = {"ms_avg": ms / launches, "launches": launches}
-        ctx.prof_reset()
-        ctx.prof_enable(True)
-        for _ in range(5):
-            step()
-        fence()
-        ctx.prof_enable(False)
-        # the same steps with the residue bytes resident in HBM (no pack, no H2D)
-        step()
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        resident_s = max_over_ranks(time.perf_counter() - t0)
-        # ... and through the public API: Alignment -> trimmer.trim -> TrimmedAlignment (its own per-thread context)
-        step_public_api()
-        api_masks = step_public_api()  # (the alignment's rows are page-locked on its second trim: once, outside the timed steps)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
+            resident_s = max_over_ranks(time.perf_counter() - t0)
+            # ... and through the public API: Alignment -> trimmer.trim -> TrimmedAlignment (its own per-thread context)
             step_public_api()
-        fence()
-        public_api_s = max_over_ranks(time.perf_counter() - t0)
-        assert np.array_equal(api_masks._res_mask, keep_res) and np.array_equal(api_masks._seq_mask, keep_seq)
-        kept = int(info.kept_residues)
-        # ... from PAGE-LOCKED rows (a copy of the alignment registered once, in front of its timed steps: every upload is then one
-        # pitched DMA copy from where the rows lie), and COLD: the first trim of a fresh Alignment through the public API (pageable rows, a context that last saw
-        # another alignment), one fresh object per sample
-        locked = a.copy()
-        step_host_rows(locked, pin=True)  # (registered here: msa_host_register, once per array)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step_host_rows(locked, pin=True)
-        fence()
-        locked_s = max_over_ranks(time.perf_counter() - t0)  # (the page-locked leg, beside the pageable headline)
-        cold = []
-        for _ in range(5):
-            fresh = Alignment(ali.names, [bytes(r) for r in a])
+            api_masks = step_public_api()  # (the alignment's rows are page-locked on its second trim: once, outside the timed steps)
             fence()
             t0 = time.perf_counter()
-            trimmer_obj.trim(fresh)
-            cold.append(time.perf_counter() - t0)
-        cold_s = max_over_ranks(float(np.median(cold)))
-        if args.workload == "C3" and not args.no_c5_leg:
-            # BASELINE config 5 behind the headline, at every N: the batch of 64 sharded over the ranks (strong scaling)
-            k5 = max(1, min(args.steps, 10))
-            e5, _, single5, kept5 = run_c5_batch(k5, max(1, min(args.warmup, 2)), with_public_api=False)
-            c5_leg = {"seconds": e5, "steps": k5, "single_gpu_s": single5, "kept": kept5}
+            for _ in range(args.steps):
+                step_public_api()
+            fence()
+            public_api_s = max_over_ranks(time.perf_counter() - t0)
+            assert np.array_equal(api_masks._res_mask, keep_res) and np.array_equal(api_masks._seq_mask, keep_seq)
+            # ... from PAGE-LOCKED rows (a copy of the alignment registered once, in front of its timed steps: every upload is then
+            # one pitched DMA copy from where the rows lie), and COLD: the first trim of a fresh Alignment through the public API
+            # (pageable rows, a context that last saw another alignment), one fresh object per sample
+            locked = a.copy()
+            step_host_rows(locked, pin=True)  # (registered here: msa_host_register, once per array)
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step_host_rows(locked, pin=True)
+            fence()
+            locked_s = max_over_ranks(time.perf_counter() - t0)  # (the page-locked leg, beside the pageable headline)
+            cold = []
+            for _ in range(5):
+                fresh = Alignment(ali.names, [bytes(r) for r in a])
+                fence()
+                t0 = time.perf_counter()
+                trimmer_obj.trim(fresh)
+                cold.append(time.perf_counter() - t0)
+            cold_s = max_over_ranks(float(np.median(cold)))
+            if args.workload == "C3" and not args.no_c5_leg:
+                # BASELINE config 5 behind the headline, at every N: the batch of 64 sharded over the ranks (strong scaling)
+                k5 = max(1, min(args.steps, 10))
+                e5, _, single5, kept5, _ = run_c5_batch(k5, max(1, min(args.warmup, 2)), with_public_api=False)
+                c5_leg = {"seconds": e5, "steps": k5, "single_gpu_s": single5, "kept": kept5}
 
-    if args.workload in ("C2", "C3") and rank == 0:
-        sim_clock = similarity_kernel_clock(a, vhash, dmat)
-    for name in ("prep", "pairs", "idstats", "gaps", "encode", "sim", "overlap", "cluster"):
-        ms, launches = ctx.prof_get(name)
-        if launches and name not in kernels:  # (pairs / sim of a resident workload: already taken from the timed region)
-            kernels[name] = {"ms_avg": ms / launches, "launches": launches}
+    if args.full:
+        if args.workload in ("C2", "C3") and rank == 0:
+            sim_clock = similarity_kernel_clock(a, vhash, dmat)
+        for name in ("prep", "pairs", "idstats", "gaps", "encode", "sim", "overlap", "cluster"):
+            ms, launches = ctx.prof_get(name)
+            if launches and name not in kernels:  # (pairs / sim of a resident workload: already taken from the timed region)
+                kernels[name] = {"ms_avg": ms / launches, "launches": launches}
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -744,12 +800,15 @@ def main():
                 "parallelism": (f"batch of {C5_BATCH} sharded over {world} rank(s) x 4 threads" if args.workload == "C5"
                                 else f"replicas x{world} (alignment per rank)"),
             },
-            "roofline": roofline,
-            "roofline_all_kernels": roofline_all,
-            "kernels_ms": {k: round(v["ms_avg"], 4) for k, v in kernels.items()},
-            "kernels_ms_source": ("HIP events: pairs and sim over the timed (host-rows) region, the other kernels over 5 untimed steps after it"
-                                  if args.workload != "C5" else "HIP events over 3 untimed trims of one alignment of the batch"),
         }
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "roofline_all_kernels": roofline_all,
+                "kernels_ms": {k: round(v["ms_avg"], 4) for k, v in kernels.items()},
+                "kernels_ms_source": ("HIP events: pairs and sim over the timed (host-rows) region, the other kernels over 5 untimed steps "
+                                      "after it" if args.workload != "C5" else "HIP events over 3 untimed trims of one alignment of the batch"),
+            })
         if c5_leg is not None:
             m5, n5, seed5 = WORKLOADS["C5"]
             out["c5_batch"] = {
@@ -776,8 +835,9 @@ def main():
             out["ms_per_step_public_api"] = round(public_api_s / args.steps * 1e3, 4)
         if args.workload != "C5":
             out["rows_page_locked"] = False  # (value / ms_per_step: ordinary pageable rows, nothing registered)
-            out["ms_per_step_median_of_5_regions"] = round(float(np.median(region_ms)), 4)
-            out["ms_per_step_regions"] = [round(x, 4) for x in region_ms]
+            if region_ms is not None:
+                out["ms_per_step_median_of_5_regions"] = round(float(np.median(region_ms)), 4)
+                out["ms_per_step_regions"] = [round(x, 4) for x in region_ms]
             if sim_clock is not None:
                 out["sim_kernel_clock_GHz"] = sim_clock
         if locked_s is not None:
@@ -792,7 +852,7 @@ def main():
         if args.workload == "C5":
             out["config"]["kept_columns_expected"] = 192501  # (tests/golden/configs.npz: the 64 masks of config 5)
             out["config"]["kept_columns_ok"] = kept == 192501
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sample = synth_msa(m, n, seed) if args.workload == "C5" else a
             ncols = args.cpu_sample_cols if args.workload != "C4" else min(args.cpu_sample_cols, 600)
             base, speedups = cpu_baseline(sample, oracle_kw, ncols, value, with_similarity=args.workload != "C4")

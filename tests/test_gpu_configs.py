@@ -305,14 +305,14 @@ def test_two_ranks_share_one_gpu():
 
 
 def test_bench_multi_rank_code_path_on_one_gpu():
-    """`python bench.py --gpus 2 --share-gpu`: the launcher, two ranks, BASELINE config 5 sharded over them through the
+    """`python bench.py --gpus 2 --share-gpu --full`: the launcher, two ranks, BASELINE config 5 sharded over them through the
     native batch path, the gather of the masks, the max-over-ranks timing and the one JSON line -- everything a
     multi-GPU run does except RCCL itself (both ranks use this box's one GPU, the process group runs over gloo)."""
     import json
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--workload", "C5", "--steps", "2", "--warmup", "1"],
-                         capture_output=True, text=True, timeout=900, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--workload", "C5", "--steps", "2", "--warmup", "1",
+                          "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -323,7 +323,7 @@ def test_bench_multi_rank_code_path_on_one_gpu():
 
 
 def test_bench_eight_ranks_dress_rehearsal_on_one_gpu():
-    """`python bench.py --gpus 8 --share-gpu --workload C5 --steps 2`: eight ranks on this box's one GPU --
+    """`python bench.py --gpus 8 --share-gpu --workload C5 --steps 2 --full`: eight ranks on this box's one GPU --
     the launcher, eight ranks x four worker contexts, config 5 sharded 8 x 8, the gather of the masks, the max-over-ranks
     timing, ONE JSON line, a clean exit of every rank -- in well under the time such a run may take.  (RCCL itself needs a
     GPU per rank; the process group runs over gloo and the line says so.)"""
@@ -332,8 +332,8 @@ def test_bench_eight_ranks_dress_rehearsal_on_one_gpu():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.perf_counter()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--workload", "C5", "--steps", "2", "--warmup", "1"],
-                         capture_output=True, text=True, timeout=600, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--workload", "C5", "--steps", "2", "--warmup", "1",
+                          "--full"], capture_output=True, text=True, timeout=600, env=env)
     seconds = time.perf_counter() - t0
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -346,13 +346,13 @@ def test_bench_eight_ranks_dress_rehearsal_on_one_gpu():
 
 
 def test_bench_default_of_a_scaling_run_on_one_gpu():
-    """`python bench.py --gpus 2 --share-gpu --steps 2` with NO --workload: what the driver's scaling run starts for N > 1.  The
+    """`python bench.py --gpus 2 --share-gpu --steps 2 --full` with NO --workload: the workload a scaling run starts for N > 1.  The
     line's `value` is the headline workload (C3, one alignment per rank per step: weak scaling, N x the 1-GPU line's work) and
     BASELINE config 5 -- the batch of 64 sharded over the ranks -- rides in the same line as `c5_batch`, all 64 masks golden."""
     import json
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -364,6 +364,45 @@ def test_bench_default_of_a_scaling_run_on_one_gpu():
     c5 = rec["c5_batch"]
     assert c5["scaling"] == "strong" and c5["n_gpus"] == 2 and c5["kept_columns"] == 192501 and c5["kept_columns_ok"] is True
     assert c5["value"] > 0 and c5["same_batch_on_rank0_alone_ms"] > 0
+
+
+def _bench_line(args, timeout):
+    import json
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, env=env)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path, golden):
+    """`python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`: a plain run prints the headline line and nothing that only
+    --full measures, and writes what its last timed step returned -- the golden C3 masks and cut points."""
+    rec = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], 300)
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and "C3" in rec["config"]["workload"]
+    assert rec["unit"] == "columns/s" and rec["higher_is_better"] is True and rec["dtype"] == "u8/f32" and rec["value"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] / 1e3 - 10000) < 10  # (columns/s x s per step = the alignment's 10 000 columns)
+    assert not {"roofline", "kernels_ms", "cpu_baseline", "c5_batch", "value_resident", "value_public_api", "value_cold"} & set(rec)
+    res, seq, info = (np.load(tmp_path / f"{name}.npy") for name in ("residues_mask", "sequences_mask", "trim_info"))
+    assert res.dtype == np.float32 and seq.dtype == np.float32 and info.dtype == np.float64
+    assert np.array_equal(res, np.unpackbits(golden["C3.res"])[:10000].astype(np.float32))
+    assert np.array_equal(seq, np.unpackbits(golden["C3.seq"])[:2000].astype(np.float32))
+    assert [info[0], info[3]] == golden["C3.cuts"].tolist()  # (selected method, gap cut)
+    assert info[5] == res.sum() == rec["config"]["kept_columns"] and info[6] == seq.sum()
+
+
+def test_bench_full_run_keeps_the_other_figures():
+    """`python bench.py --gpus 1 --full --no-cpu-baseline`: the legs beside the headline -- resident, public API, page-locked,
+    cold, five regions, per-kernel times and roofline, config 5 behind C3 -- are all still measured under --full."""
+    rec = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], 600)
+    assert rec["steps"] == 2 and rec["value"] > 0 and rec["ms_per_step"] > 0 and "cpu_baseline" not in rec
+    assert rec["roofline"]["kernel"] in ("sim", "pairs") and rec["roofline_all_kernels"] and rec["kernels_ms"]
+    for key in ("value_resident", "value_public_api", "value_page_locked_rows", "value_cold"):
+        assert rec[key] > 0, key
+    assert len(rec["ms_per_step_regions"]) == 5 and rec["ms_per_step_median_of_5_regions"] > 0
+    assert rec["c5_batch"]["kept_columns_ok"] is True
 
 
 def _launcher_env():

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT
 for w in C3 C2 C4 C5; do
-  timeout 900 python bench.py --steps 20 --warmup 3 --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; echo "bench $w rc=$?"
+  timeout 900 python bench.py --full --steps 20 --warmup 3 --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; echo "bench $w rc=$?"
 done
 export TMPDIR=/tmp
 cd /tmp

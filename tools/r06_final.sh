@@ -4,8 +4,8 @@ export MSA_DIAGNOSTICS=1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r06_final
 rm -rf $OUT; mkdir -p $OUT; cd $ROOT
-timeout 900 python bench.py --steps 20 --warmup 3 --workload C5 > $OUT/bench_C5.json 2> $OUT/bench_C5.err; echo "bench C5 rc=$?"
-timeout 900 python bench.py --steps 20 --warmup 3 --workload C3 > $OUT/bench_C3.json 2> $OUT/bench_C3.err; echo "bench C3 rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 3 --workload C5 > $OUT/bench_C5.json 2> $OUT/bench_C5.err; echo "bench C5 rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 3 --workload C3 > $OUT/bench_C3.json 2> $OUT/bench_C3.err; echo "bench C3 rc=$?"
 timeout 300 python tools/c5_counts.py > $OUT/c5_counts.jsonl 2>/dev/null
 timeout 300 python tools/small_latency.py > $OUT/small_latency.jsonl 2>/dev/null
 timeout 600 python -m torch.distributed.run --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29547 tools/c5_collective.py 15 > $OUT/c5_collective.jsonl 2> $OUT/c5_collective.err

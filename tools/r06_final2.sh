@@ -8,9 +8,9 @@ timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.txt 2>&1; ech
 timeout 1500 python tools/tall_halves_ab.py > $OUT/tall_halves_ab.jsonl 2>/dev/null; echo "halves ab rc=$?"
 for rep in 1 2; do for v in "MSA_LG_HALVES=1" "MSA_LG_HALVES=0"; do
   echo "== C3 $v" >> $OUT/c3_halves.txt
-  env $v timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['ms_per_step'], r.get('ms_per_step_median_of_5_regions'), r.get('ms_per_step_resident'), r.get('kernels_ms'))" >> $OUT/c3_halves.txt
+  env $v timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['ms_per_step'], r.get('ms_per_step_median_of_5_regions'), r.get('ms_per_step_resident'), r.get('kernels_ms'))" >> $OUT/c3_halves.txt
 done; done
-timeout 900 python bench.py --steps 20 --warmup 3 --workload C3 > $OUT/bench_C3.json 2> $OUT/bench_C3.err; echo "bench C3 rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 3 --workload C3 > $OUT/bench_C3.json 2> $OUT/bench_C3.err; echo "bench C3 rc=$?"
 timeout 600 python bench.py --workload REF --out $OUT/reference_shape.jsonl > $OUT/bench_REF.json 2> $OUT/bench_REF.err
 timeout 600 python tools/sim_shapes.py > $OUT/sim_shapes.jsonl 2>/dev/null
 export TMPDIR=/tmp; cd /tmp
