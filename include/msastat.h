@@ -166,6 +166,27 @@ int msa_clustal_scan(const uint8_t *data, int64_t len, int32_t *m_out, int32_t *
 int msa_clustal_fill(const uint8_t *data, int64_t len, int32_t m, int32_t n, uint8_t *matrix, int64_t *name_off,
                      int32_t *name_len, const uint8_t *valid, msa_err_detail *detail);
 
+/* ---- FASTA text parsed on the device: `Alignment.load(file, "fasta")` without host rows.  The text is copied to the device
+ *      as it is and kernels write the context's residue matrix: what msa_upload_packed would hold for the matrix msa_fasta_fill
+ *      produces from the same text (same m, n, bytes, device pitch with zero padding, failures and their detail). ----------- */
+typedef struct {
+    int32_t m, n;       /* records (0: no header line) and residues per record */
+    uint32_t seq_type;  /* SequenceTypes bits of the matrix (DNA 1, RNA 2, AA 4, degenerate 8; 0 when m * n == 0): what
+                           pytrimal_amd's detect_alignment_type returns, i.e. trimAl's getAlignmentType (_trimal.pyx:891) */
+} msa_text_info;
+/* text[len] (host memory, len < 2^31; longer texts: MSA_E_INVALID) -> the context's alignment, indet 'X' when seq_type & 4 and
+ * 'N' otherwise.  valid: the 256-entry table of accepted residue bytes, as for msa_fasta_fill (nullable: every byte).  Returns
+ * MSA_OK (m == 0 included: the context then holds an empty alignment), MSA_E_BAD_RESIDUE or MSA_E_LENGTH_MISMATCH with
+ * detail as msa_fasta_fill reports it (the first failure in stream order; info->m and ->n are the text's, the context holds
+ * an empty alignment).  Waits for the stream: the shape and the failure are needed on the host. */
+int msa_upload_fasta(msa_ctx *ctx, const uint8_t *text, int64_t len, const uint8_t *valid, msa_text_info *info,
+                     msa_err_detail *detail);
+/* the records' names of the last msa_upload_fasta (name_off[m] / name_len[m] into its text; m = info->m, also after
+ * MSA_E_BAD_RESIDUE and MSA_E_LENGTH_MISMATCH), or MSA_E_INVALID when it stopped before the records */
+int msa_text_names(msa_ctx *ctx, int64_t *name_off, int32_t *name_len);
+/* the context's residue matrix -> host rows[m][ld] (ld >= n; the bytes behind n of a row are not written) */
+int msa_download_rows(msa_ctx *ctx, uint8_t *rows, int64_t ld);
+
 /* ---- whole trim: trimAlManager::clean_alignment (manager.pxd:88) as configured by the four
  *      `_configure_manager` methods (_trimal.pyx:1479-1497,1651-1659,1766-1769,1859-1862) ------ */
 enum {
@@ -238,6 +259,18 @@ int32_t msa_batch_workers(const msa_batch *b);
 int msa_trim_batch(msa_batch *b, int32_t count, const uint8_t *const *data, const int32_t *m, const int32_t *n,
                    const int64_t *ld, const uint8_t *indet, const msa_trim_params *params, uint8_t *const *keep_res,
                    uint8_t *const *keep_seq, msa_trim_info *info, int32_t *rc);
+/* The same for FASTA texts: texts[k] of lens[k] bytes, parsed by msa_upload_fasta (valid as there), trimmed with
+ * params_by_type[0] (amino acids, and an undetected type), [1] (nucleotides) or [2] (degenerate nucleotides) by the parsed
+ * type -- the choice pytrimal_amd's trimmer._prepare makes.  The workers take the texts largest first; with want_rows each
+ * also downloads the matrix.  Returns MSA_OK or the first non-zero rc[k].  msa_batch_fasta_result reads text k's results
+ * (every output nullable; owned by the batch object, valid until its next call): the parse, the masks, the names, the rows
+ * (want_rows), the trim's info, the failure's detail.  It returns what msa_upload_fasta returned for text k (or
+ * MSA_E_INVALID for an index outside the last call). */
+int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                         const msa_trim_params params_by_type[3], int32_t want_rows, int32_t *rc);
+int msa_batch_fasta_result(msa_batch *b, int32_t k, msa_text_info *info, const uint8_t **keep_res, const uint8_t **keep_seq,
+                           const int64_t **name_off, const int32_t **name_len, const uint8_t **rows, msa_trim_info *tinfo,
+                           msa_err_detail *detail);
 /* the rows behind MSA_W_ONLY_GAPS_SEQUENCES of alignment k of the last call (as msa_trim_only_gaps_rows) */
 int msa_batch_only_gaps_rows(msa_batch *b, int32_t k, int32_t *rows, int32_t cap);
 const char *msa_batch_last_hip_error(const msa_batch *b, int32_t worker);
@@ -272,7 +305,8 @@ enum {
     MSA_PATH_UPLOAD_PITCHED = 3,  /* one pitched copy straight from the caller's rows */
     MSA_PATH_UPLOAD_PACKED = 4,   /* packed into pinned pieces, each sent as soon as it is packed */
     MSA_PATH_UPLOAD_ATTACHED = 5, /* msa_attach_device */
-    MSA_PATH_UPLOAD_REPITCHED = 6 /* a contiguous pageable matrix of odd-sized rows: one linear copy, then a kernel lays the rows out at the device pitch */
+    MSA_PATH_UPLOAD_REPITCHED = 6, /* a contiguous pageable matrix of odd-sized rows: one linear copy, then a kernel lays the rows out at the device pitch */
+    MSA_PATH_UPLOAD_FASTA = 7      /* msa_upload_fasta: the text copied as it is, parsed into the device layout by kernels */
 };
 enum {
     MSA_PATH_PIPE_NONE = 0,

@@ -46,6 +46,7 @@ EXPORTS = [
     "msa_representatives", "msa_cutpoint_clusters", "msa_trim", "msa_trim_only_gaps_rows", "msa_batch_create", "msa_batch_destroy", "msa_batch_workers", "msa_trim_batch",
     "msa_batch_only_gaps_rows", "msa_batch_last_hip_error", "msa_prof_get", "msa_prof_reset",
     "msa_prof_enable", "msa_debug_sim_launches", "msa_debug_last_paths", "msa_debug_switches_enabled", "msa_fasta_scan", "msa_fasta_fill", "msa_clustal_scan", "msa_clustal_fill",
+    "msa_upload_fasta", "msa_text_names", "msa_download_rows", "msa_trim_batch_fasta", "msa_batch_fasta_result",
 ]
 
 
@@ -89,7 +90,14 @@ class TrimInfo(ctypes.Structure):
     ]
 
 
+class TextInfo(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int32), ("n", ctypes.c_int32), ("seq_type", ctypes.c_uint32)]
+
+
 W_ONLY_GAPS_SEQUENCES, W_NO_COLUMNS_LEFT, W_UNDEFINED_IDENTITY = 1, 2, 4
+
+# the longest text msa_upload_fasta parses (32-bit offsets in its kernels)
+FASTA_MAX_BYTES = (1 << 31) - 1
 
 
 _lib = None
@@ -167,6 +175,13 @@ def load():
         L.msa_batch_only_gaps_rows.argtypes = [vp, i32, vp, i32]
         L.msa_batch_last_hip_error.argtypes = [vp, i32]
         L.msa_batch_last_hip_error.restype = ctypes.c_char_p
+        L.msa_upload_fasta.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.POINTER(TextInfo), ctypes.POINTER(ErrDetail)]
+        L.msa_text_names.argtypes = [vp, vp, vp]
+        L.msa_download_rows.argtypes = [vp, vp, ctypes.c_int64]
+        L.msa_trim_batch_fasta.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp]
+        pp = ctypes.POINTER(vp)
+        L.msa_batch_fasta_result.argtypes = [vp, i32, ctypes.POINTER(TextInfo), pp, pp, pp, pp, pp, ctypes.POINTER(TrimInfo),
+                                             ctypes.POINTER(ErrDetail)]
         L.msa_prof_get.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(f32), ctypes.POINTER(i32)]
         L.msa_prof_reset.argtypes = [vp]
         L.msa_prof_reset.restype = None
@@ -357,6 +372,39 @@ class Context:
         check(self.lib, self.h, self.lib.msa_upload_rows(self.h, ptrs, m, n, indet))
         self.shape = (m, n)
 
+    def upload_fasta(self, text, valid=None):
+        """FASTA text (bytes-like) -> this context's alignment, parsed on the device (`msa_upload_fasta`); `valid`: the
+        256-entry table of accepted residue bytes (default: `Alignment.load`'s).  Returns the `TextInfo` (m, n, seq_type);
+        a text that does not parse raises `MsaError` with the code and detail of `msa_fasta_fill`."""
+        if valid is None:
+            from .alignment import _VALID
+
+            valid = _VALID
+        valid = np.ascontiguousarray(valid, dtype=np.uint8)
+        buf = np.frombuffer(text, dtype=np.uint8)
+        info, det = TextInfo(), ErrDetail()
+        rc = self.lib.msa_upload_fasta(self.h, ptr(buf), buf.size, ptr(valid), ctypes.byref(info), ctypes.byref(det))
+        self.shape = (info.m, info.n) if rc == OK else (0, 0)
+        self._in_flight = None
+        self.text_info = info
+        check(self.lib, self.h, rc, det)
+        return info
+
+    def text_names(self):
+        """(offsets int64[m], lengths int32[m]) of the records' names in the last `upload_fasta`'s text."""
+        m = self.text_info.m
+        off = np.zeros(m, dtype=np.int64)
+        ln = np.zeros(m, dtype=np.int32)
+        check(self.lib, self.h, self.lib.msa_text_names(self.h, ptr(off), ptr(ln)))
+        return off, ln
+
+    def download_rows(self):
+        """The context's residue matrix as host rows: uint8[m, n]."""
+        m, n = self.shape
+        out = np.zeros((m, n), dtype=np.uint8)
+        check(self.lib, self.h, self.lib.msa_download_rows(self.h, ptr(out), max(n, 1)))
+        return out
+
     def attach(self, dev_ptr, m, n, ld, indet):
         check(self.lib, self.h, self.lib.msa_attach_device(self.h, ctypes.c_void_p(dev_ptr), m, n, ld, indet))
         self.shape = (m, n)
@@ -451,7 +499,7 @@ class Context:
 
     PATH_KEYS = ("upload", "pipeline", "sim_kernel", "sim_waves_per_column", "sim_launches", "sim_writes_mdk", "pair_kernel", "pair_waves_per_tile")
     PATH_NAMES = {
-        "upload": ("none", "in_place", "linear", "pitched", "packed", "attached", "repitched"),
+        "upload": ("none", "in_place", "linear", "pitched", "packed", "attached", "repitched", "fasta"),
         "pipeline": ("none", "serial", "one_stream", "two_streams", "compact", "compact_gaps", "compact_sorted"),
         "sim_kernel": ("none", "flat", "lg", "lg_big", "seq", "cols", "lg_pipe", "lg_big_pipe", "lg_xseg", "lg_big_xseg"),
         "pair_kernel": ("none", "pipe", "two_rows", "pipe16"),
@@ -575,6 +623,59 @@ class Batch:
                         self.lib.msa_batch_only_gaps_rows(self.h, k, ptr(buf), cnt)
                         rows = [int(r) for r in buf]
                 out.append((flags[pos:pos + n], flags[pos + n:pos + n + m], infos[k], rc, rows))
+        return out
+
+    def trim_fasta(self, texts, valid, params3, want_rows=False):
+        """`texts`: FASTA texts (bytes-like, each < 2^31 bytes), `params3`: `TrimParams * 3` by type (msa_trim_batch_fasta)
+        -> per text a dict: parse_rc, info (TextInfo), keep_res / keep_seq (bool, copies), name_off / name_len, rows
+        (uint8[m, n] with `want_rows`, else None), tinfo (TrimInfo), detail, rc, only_gaps_rows.  The interpreter lock is
+        released for the whole call."""
+        count = len(texts)
+        if count == 0:
+            return []
+        bufs = [np.frombuffer(t, dtype=np.uint8) for t in texts]
+        addr = np.array([b.ctypes.data if b.size else 0 for b in bufs], dtype=np.uint64)
+        lens = np.array([b.size for b in bufs], dtype=np.int64)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8)
+        rcs = np.zeros(count, dtype=np.int32)
+        out = []
+        with self._lock:
+            if not self.h:
+                raise BatchClosed("the batch object is closed")
+            rc_all = self.lib.msa_trim_batch_fasta(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3, int(bool(want_rows)),
+                                                   ptr(rcs))
+            if rc_all != OK and not rcs.any():
+                raise MsaError(rc_all, self.lib.msa_strerror(rc_all).decode())
+            info, tinfo, det = TextInfo(), TrimInfo(), ErrDetail()
+            p_res, p_seq, p_off, p_len, p_rows = (ctypes.c_void_p() for _ in range(5))
+            for k in range(count):
+                parse_rc = self.lib.msa_batch_fasta_result(self.h, k, ctypes.byref(info), ctypes.byref(p_res), ctypes.byref(p_seq),
+                                                           ctypes.byref(p_off), ctypes.byref(p_len), ctypes.byref(p_rows),
+                                                           ctypes.byref(tinfo), ctypes.byref(det))
+                m, n = info.m, info.n
+
+                def grab(p, count, ctype, dtype):
+                    if not p.value or count == 0:
+                        return np.zeros(count, dtype=dtype)
+                    return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
+
+                parsed = parse_rc == OK
+                rec = {
+                    "parse_rc": parse_rc, "info": TextInfo(m, n, info.seq_type), "rc": int(rcs[k]),
+                    "tinfo": TrimInfo.from_buffer_copy(tinfo), "detail": ErrDetail.from_buffer_copy(det),
+                    "keep_res": grab(p_res, n if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
+                    "keep_seq": grab(p_seq, m if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
+                    "name_off": grab(p_off, m, ctypes.c_int64, np.int64), "name_len": grab(p_len, m, ctypes.c_int32, np.int32),
+                    "rows": grab(p_rows, m * n, ctypes.c_uint8, np.uint8).reshape(m, n) if (want_rows and parsed and p_rows.value) else None,
+                    "only_gaps_rows": [],
+                }
+                if parsed and tinfo.warnings & W_ONLY_GAPS_SEQUENCES:
+                    cnt = self.lib.msa_batch_only_gaps_rows(self.h, k, None, 0)
+                    if cnt > 0:
+                        buf = np.empty(cnt, dtype=np.int32)
+                        self.lib.msa_batch_only_gaps_rows(self.h, k, ptr(buf), cnt)
+                        rec["only_gaps_rows"] = [int(r) for r in buf]
+                out.append(rec)
         return out
 
     def check(self, rc, info):

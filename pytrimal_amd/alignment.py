@@ -9,6 +9,7 @@ trimAl's ten-format `FormatHandling` layer is I/O, not statistics (SURVEY.md sec
 """
 import io
 import os
+import stat
 
 import numpy as np
 
@@ -232,30 +233,15 @@ class Alignment:
     @classmethod
     def load(cls, file, format=None):
         """Load a multiple sequence alignment from a path or a binary file-like object."""
-        if file is None:
-            raise TypeError("`file` must not be None")
-        if isinstance(file, (str, bytes, os.PathLike)):
-            path = os.fspath(file)
-            if os.path.isdir(path):
-                raise IsADirectoryError(file)
-            with open(path, "rb") as f:
-                data = f.read()
-            fmt = format
-        else:
-            ty = type(file).__name__
-            if not hasattr(file, "seek") or not file.seekable():
-                raise TypeError(f"{ty!r} object is not seekable.")
-            if not hasattr(file, "readinto") and not hasattr(file, "read"):
-                raise TypeError(f"{ty!r} object has no attribute 'read'.")
-            if format is None:
-                raise ValueError("Format must be specified when loading from a file-like object")
-            data = file.read()
-            if isinstance(data, str):
-                raise TypeError(f"{ty!r} object is not open in binary mode.")
-            fmt = format
+        data = _read_input(file, format)
+        fmt = format
         if fmt is None:
             fmt = _sniff_format(data)
-        fmt = fmt.lower()
+        return cls._from_text(data, file, format, fmt.lower())
+
+    @classmethod
+    def _from_text(cls, data, file, format, fmt):
+        """`load` behind the read: the text of `file` in the (lower-case) format `fmt`."""
         if fmt in ("fasta", "clustal"):
             fast = _load_native(cls, data, file, fmt)
             if fast is not None:
@@ -438,6 +424,47 @@ class TrimmedAlignment(Alignment):
 
 
 # --- minimal readers --------------------------------------------------------------------------
+
+def _read_input(file, format, mapped=False):
+    """The bytes of a path or a binary file-like object, with `Alignment.load`'s checks and messages.  `mapped`: a path to a
+    non-empty regular file is mapped read-only instead of read (an `mmap` object); anything else a path names -- a pipe, a
+    FIFO, a character device, a /proc file, which report no size -- and an empty file are read as `Alignment.load` reads
+    them.  A mapped file must not be truncated while the mapping is in use: reading the pages past its new end raises
+    SIGBUS, where a read would not."""
+    if file is None:
+        raise TypeError("`file` must not be None")
+    if isinstance(file, (str, bytes, os.PathLike)):
+        path = os.fspath(file)
+        if os.path.isdir(path):
+            raise IsADirectoryError(file)
+        with open(path, "rb") as f:
+            st = os.fstat(f.fileno()) if mapped else None
+            if st is None or not stat.S_ISREG(st.st_mode) or st.st_size == 0:
+                return f.read()
+            import mmap
+
+            return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    ty = type(file).__name__
+    if not hasattr(file, "seek") or not file.seekable():
+        raise TypeError(f"{ty!r} object is not seekable.")
+    if not hasattr(file, "readinto") and not hasattr(file, "read"):
+        raise TypeError(f"{ty!r} object has no attribute 'read'.")
+    if format is None:
+        raise ValueError("Format must be specified when loading from a file-like object")
+    data = file.read()
+    if isinstance(data, str):
+        raise TypeError(f"{ty!r} object is not open in binary mode.")
+    return data
+
+
+def _sniff_mapped(data):
+    """`_sniff_format` of a text that may be mapped: decided on its first 4 KB where they decide it (FASTA, PIR, Clustal,
+    NEXUS, MEGA), on the whole text otherwise."""
+    head = bytes(data[:4096]).lstrip()
+    if (head[:1] == b">" and len(head) >= 4) or head[:8].upper().startswith((b"CLUSTAL", b"#NEXUS", b"#MEGA")):
+        return _sniff_format(head)
+    return _sniff_format(bytes(data))
+
 
 def _load_native(cls, data, file, fmt):
     """FASTA / Clustal text -> Alignment through the native ingest of libmsastat (`msa_fasta_scan` / `msa_fasta_fill`,

@@ -272,3 +272,129 @@ def _rebuild(alignment, keep_res, keep_seq, gap_stats=False):
     out = TrimmedAlignment._from_parts(alignment._names if whole else alignment.names, dense, alignment._datatype, keep_seq, keep_res)
     out._gap_stats = gap_stats  # (what `terminal_only` counts over: trimmer._finish)
     return out
+
+
+# ---- files -> masks: FASTA parsed on the device ----------------------------------------------------------------------------
+# Every non-empty FASTA text goes to the device, whatever its size: the device parse was faster at every size measured
+# (tools/from_files.py, profiles/r07_from_files.jsonl: 1024 files of 100 x 1000 (102 KB each) 99 ms against 207 ms through
+# Alignment.load + trim_batch, the C5 set 57 ms against 225), so there is no threshold below which small files take the host path.
+
+
+def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, threads=6, device=None):
+    """Trim the alignments in `files` (paths or binary file objects) on this process's device.
+
+    Returns and raises what ``trim_batch(trimmer, [Alignment.load(f, format) for f in files], matrix, shard=False,
+    masks_only=masks_only)`` does, but FASTA texts never become host rows: each is copied to the device as it is and parsed
+    there into the alignment's device layout (`msa_trim_batch_fasta`, include/msastat.h), then trimmed by the native
+    workers (`threads` of them) with the matrix of its type.  Other formats, and texts the device does not parse (empty,
+    longer than 2^31 - 1 bytes), go through `Alignment.load` and the row path in the same call.  Results come in input
+    order; the failure of the first file (in input order) that does not load is raised before any trim failure.
+    """
+    from . import _lib
+    from .alignment import _VALID, _read_input, _sniff_format, _sniff_mapped
+    from .matrix import SimilarityMatrix
+
+    files = list(files)
+    if getattr(trimmer, "_platform", None) != "hip" or not (matrix is None or isinstance(matrix, SimilarityMatrix)):
+        # (no device, or a matrix `trim` refuses: the composition itself, which raises what it raises where it raises it)
+        return trim_batch(trimmer, [Alignment.load(f, format) for f in files], matrix, device=device, threads=threads, shard=False,
+                          masks_only=masks_only)
+    texts, failed = [], None  # (data, fmt) per file up to the first that cannot be read
+    for k, f in enumerate(files):
+        try:
+            data = _read_input(f, format, mapped=True)
+            fmt = format if format is not None else (_sniff_format(data) if isinstance(data, bytes) else _sniff_mapped(data))
+            texts.append((data, fmt.lower()))
+        except Exception as err:
+            failed = (k, err)
+            break
+    on_device = [k for k, (data, fmt) in enumerate(texts) if fmt == "fasta" and 0 < len(data) <= _lib.FASTA_MAX_BYTES]
+    params3, _keep = trimmer._fasta_params(matrix)
+    index = device.index if isinstance(device, torch.device) and device.index is not None else None
+    if index is None:
+        index = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    workers = max(1, min(int(threads), 64))
+
+    def run(call):
+        for attempt in range(3):
+            batch = _native_batch(index, workers)
+            try:
+                return batch, call(batch)
+            except _lib.BatchClosed:  # (another thread replaced the device's batch object)
+                if attempt == 2:
+                    raise
+
+    done = {}
+    if on_device:
+        batch, outs = run(lambda b: b.trim_fasta([texts[k][0] for k in on_device], _VALID.view(np.uint8), params3,
+                                                  want_rows=not masks_only))
+        for k, rec in zip(on_device, outs):
+            if rec["parse_rc"] not in (_lib.OK, _lib.E_BAD_RESIDUE, _lib.E_LENGTH_MISMATCH):
+                batch.check(rec["parse_rc"], rec["tinfo"])  # a device failure (HIP, memory) is raised, never hidden behind the host path
+            if rec["info"].m > 0 and rec["info"].n > 0:
+                rec["batch"] = batch
+                done[k] = rec
+    # the rest, and the texts without a record or with empty records, as Alignment.load reads them (its messages)
+    loaded, errors = {}, {}
+    for k, (data, fmt) in enumerate(texts):
+        if k not in done:
+            try:
+                loaded[k] = Alignment._from_text(data if isinstance(data, bytes) else bytes(data), files[k], format, fmt)
+            except Exception as err:
+                errors[k] = err
+    if failed is not None:
+        errors[failed[0]] = failed[1]
+    for k in range(len(texts) + (failed is not None)):  # the first file that does not load, in input order
+        if k in errors:
+            raise errors[k]
+        if k in done and done[k]["parse_rc"] != _lib.OK:
+            raise _fasta_error(done[k], texts[k][0])
+    # the loaded ones through the row path (what trim_batch does with them)
+    prepared = {k: trimmer._prepare(a, matrix) for k, a in loaded.items()}
+    rows_todo = [k for k, p in prepared.items() if p[1].shape[0] and p[1].shape[1]]
+    if rows_todo:
+        batch, outs = run(lambda b: b.trim([(prepared[k][1], prepared[k][2], prepared[k][3]) for k in rows_todo]))
+        for k, o in zip(rows_todo, outs):
+            done[k] = {"rc": o[3], "tinfo": o[2], "batch": batch, "keep_res": o[0], "keep_seq": o[1], "only_gaps_rows": o[4]}
+    for k in sorted(done):  # trim failures, in input order
+        if done[k]["rc"] != _lib.OK:
+            done[k]["batch"].check(done[k]["rc"], done[k]["tinfo"])
+    out = []
+    for k, (data, _) in enumerate(texts):
+        rec = done.get(k)
+        if k in prepared:
+            names, dense, _, params, _ = prepared[k]
+            if rec is None:  # an empty alignment never reaches the device
+                rec = {"keep_res": np.ones(dense.shape[1], dtype=bool), "keep_seq": np.ones(dense.shape[0], dtype=bool), "tinfo": None,
+                       "only_gaps_rows": None}
+            datatype, ty = loaded[k]._datatype, None
+        else:
+            names, dense, ty = None, rec["rows"], rec["info"].seq_type
+            params, datatype = params3[0 if (ty & 4 or ty == 0) else (2 if ty & 8 else 1)], 0
+        tinfo = rec["tinfo"]
+        if masks_only:
+            if tinfo is not None and tinfo.warnings:
+                _raise_warnings(tinfo, names if names is not None else _fasta_names(rec, data), rec["only_gaps_rows"])
+            out.append((np.asarray(rec["keep_res"], dtype=bool), np.asarray(rec["keep_seq"], dtype=bool)))
+            continue
+        t = trimmer._finish(names if names is not None else _fasta_names(rec, data), dense, datatype, rec["keep_res"], rec["keep_seq"],
+                            tinfo, rec["only_gaps_rows"], None, params)
+        if ty is not None and rec["keep_res"].all() and rec["keep_seq"].all():
+            t._detected_type = ty  # (nothing removed: the type the device detected is the result's)
+        out.append(t)
+    return out
+
+
+def _fasta_names(rec, data):
+    return [bytes(data[o:o + n]) for o, n in zip(rec["name_off"].tolist(), rec["name_len"].tolist())]
+
+
+def _fasta_error(rec, data):
+    """The ValueError `Alignment.load` raises for this parse failure (alignment._load_native)."""
+    from . import _lib
+
+    d = rec["detail"]
+    if rec["parse_rc"] == _lib.E_LENGTH_MISMATCH:
+        return ValueError(f"Sequence length mismatch in sequence {d.row}: {d.col} != {rec['info'].n}")
+    name = _fasta_names(rec, data)[d.row]
+    return ValueError(f"The sequence \"{name.decode('ascii', 'replace')}\" has an unknown ({d.byte}) character")

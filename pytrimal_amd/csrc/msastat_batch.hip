@@ -48,6 +48,22 @@ struct msa_batch {
     double engine_max_work = 3e8;                 // m * m * n up to which the engine takes an alignment (MSA_BATCH_ENGINE_MAX)
     int engine_min_count = 40;                    // fewer eligible alignments than this go to the workers instead (MSA_BATCH_ENGINE_MIN)
     bool in_call = false;
+    // a call of msa_trim_batch_fasta (texts != nullptr): the texts, and what each of them gave (kept until the next call)
+    const uint8_t *const *texts = nullptr;
+    const int64_t *lens = nullptr;
+    const uint8_t *valid = nullptr;
+    const msa_trim_params *params_by_type = nullptr;
+    bool want_rows = false;
+    struct FastaResult {
+        int parse_rc = MSA_OK;
+        msa_text_info info{};
+        msa_trim_info tinfo{};
+        msa_err_detail detail{};
+        std::vector<uint8_t> keep_res, keep_seq, rows;
+        std::vector<int64_t> name_off;
+        std::vector<int32_t> name_len;
+    };
+    std::vector<FastaResult> fasta;
 };
 
 // ---- the batch engine: one launch per kernel family for a whole group of alignments -------------------------------------
@@ -700,6 +716,40 @@ int engine_run(msa_batch *b, const std::vector<int32_t> &ks) {
 }  // namespace msai
 
 namespace msai {
+// one text of msa_trim_batch_fasta on worker context c: parse, trim with the parameters of its type, names (and rows)
+int fasta_item(msa_batch *b, msa_ctx *c, int32_t k) {
+    msa_batch::FastaResult &r = b->fasta[k];
+    r.parse_rc = msa_upload_fasta(c, b->texts[k], b->lens[k], b->valid, &r.info, &r.detail);
+    const int m = r.info.m, n = r.info.n;
+    if (r.parse_rc != MSA_OK) {  // (a failure names its record: the names came with the parse)
+        if ((r.parse_rc == MSA_E_BAD_RESIDUE || r.parse_rc == MSA_E_LENGTH_MISMATCH) && m > 0) {
+            r.name_off.resize((size_t)m);
+            r.name_len.resize((size_t)m);
+            if (msa_text_names(c, r.name_off.data(), r.name_len.data()) != MSA_OK) r.name_off.clear(), r.name_len.clear();
+        }
+        return r.parse_rc;
+    }
+    const uint32_t ty = r.info.seq_type;
+    r.keep_res.assign((size_t)n, 1);
+    r.keep_seq.assign((size_t)m, 1);
+    int rc = MSA_OK;
+    if (m > 0 && n > 0) {  // (an empty alignment never reaches the device: trim_batch)
+        const msa_trim_params *p = b->params_by_type + ((ty & 4) || ty == 0 ? 0 : ((ty & 8) ? 2 : 1));
+        rc = msa_trim(c, p, r.keep_res.data(), r.keep_seq.data(), &r.tinfo);
+        b->only_gaps[k] = c->only_gaps_rows;
+        if (rc == MSA_OK && b->want_rows) {
+            r.rows.resize((size_t)m * n);
+            rc = msa_download_rows(c, r.rows.data(), n);
+        }
+    }
+    if (rc == MSA_OK && m > 0) {
+        r.name_off.resize((size_t)m);
+        r.name_len.resize((size_t)m);
+        rc = msa_text_names(c, r.name_off.data(), r.name_len.data());
+    }
+    return rc;
+}
+
 void batch_worker(msa_batch *b, int w) {
     (void)hipSetDevice(b->device);
     uint64_t seen = 0, seen_sel = 0;
@@ -734,8 +784,9 @@ void batch_worker(msa_batch *b, int w) {
             int rc;
             try {  // (an exception must not leave the thread: std::terminate would take the caller's process with it)
                 c->only_gaps_rows.clear();
-                rc = msa_upload_packed_async(c, b->data[k], b->m[k], b->n[k], b->ld[k], b->indet[k]);
-                if (rc == MSA_OK) rc = msa_trim(c, b->params + k, b->keep_res[k], b->keep_seq[k], info);
+                if (b->texts) rc = fasta_item(b, c, k);
+                else if ((rc = msa_upload_packed_async(c, b->data[k], b->m[k], b->n[k], b->ld[k], b->indet[k])) == MSA_OK)
+                    rc = msa_trim(c, b->params + k, b->keep_res[k], b->keep_seq[k], info);
                 else {
                     std::memset(info, 0, sizeof(*info));
                     (void)hipStreamSynchronize(c->stream);  // (nothing of a failed upload may stay in flight over the caller's rows)
@@ -846,6 +897,7 @@ int msa_trim_batch(msa_batch *b, int32_t count, const uint8_t *const *data, cons
             engine_ks.clear();
         }
         b->only_gaps.assign(count, {});
+        b->fasta.clear();  // (msa_batch_fasta_result: results of the last call only)
         for (int32_t k = 0; k < count; ++k) rc[k] = MSA_OK;
         b->next.store(0);
         b->running = b->order.empty() ? 0 : (int)b->workers.size();
@@ -878,6 +930,55 @@ int msa_trim_batch(msa_batch *b, int32_t count, const uint8_t *const *data, cons
     for (int32_t k = 0; k < count; ++k)
         if (rc[k] != MSA_OK) return rc[k];
     return MSA_OK;
+}
+
+int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                         const msa_trim_params params_by_type[3], int32_t want_rows, int32_t *rc) {
+    if (!b || count < 0 || (count > 0 && (!texts || !lens || !params_by_type || !rc))) return MSA_E_INVALID;
+    if (count == 0) return MSA_OK;
+    {
+        std::unique_lock<std::mutex> lk(b->mu);
+        if (b->running || b->in_call) return MSA_E_INVALID;  // one call at a time per batch object
+        b->in_call = true;
+        b->count = count;
+        b->texts = texts, b->lens = lens, b->valid = valid, b->params_by_type = params_by_type, b->want_rows = want_rows != 0;
+        b->info = nullptr, b->rc = rc;
+        b->order.resize(count);
+        for (int32_t k = 0; k < count; ++k) b->order[k] = k;
+        std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return lens[x] > lens[y]; });  // largest first
+        b->fasta.assign(count, msa_batch::FastaResult());
+        b->only_gaps.assign(count, {});
+        for (int32_t k = 0; k < count; ++k) rc[k] = MSA_OK;
+        b->next.store(0);
+        b->running = (int)b->workers.size();
+        ++b->generation;
+    }
+    b->cv_work.notify_all();
+    {
+        std::unique_lock<std::mutex> lk(b->mu);
+        b->cv_done.wait(lk, [&] { return b->running == 0; });
+        b->in_call = false;
+        b->texts = nullptr;
+    }
+    for (int32_t k = 0; k < count; ++k)
+        if (rc[k] != MSA_OK) return rc[k];
+    return MSA_OK;
+}
+
+int msa_batch_fasta_result(msa_batch *b, int32_t k, msa_text_info *info, const uint8_t **keep_res, const uint8_t **keep_seq,
+                           const int64_t **name_off, const int32_t **name_len, const uint8_t **rows, msa_trim_info *tinfo,
+                           msa_err_detail *detail) {
+    if (!b || k < 0 || k >= (int32_t)b->fasta.size()) return MSA_E_INVALID;
+    const msa_batch::FastaResult &r = b->fasta[k];
+    if (info) *info = r.info;
+    if (keep_res) *keep_res = r.keep_res.data();
+    if (keep_seq) *keep_seq = r.keep_seq.data();
+    if (name_off) *name_off = r.name_off.data();
+    if (name_len) *name_len = r.name_len.data();
+    if (rows) *rows = r.rows.empty() ? nullptr : r.rows.data();
+    if (tinfo) *tinfo = r.tinfo;
+    if (detail) *detail = r.detail;
+    return r.parse_rc;
 }
 
 int msa_batch_only_gaps_rows(msa_batch *b, int32_t k, int32_t *rows, int32_t cap) {

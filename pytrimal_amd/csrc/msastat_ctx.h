@@ -223,6 +223,15 @@ struct msa_ctx {
     // [6] pair kernel, [7] its waves per tile
     int32_t paths[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
+    // msa_upload_fasta: the text as it came, the parse's scratch (tile summaries and start states) and results
+    DevBuf<uint8_t> fa_text;
+    DevBuf<char> fa_work;
+    DevBuf<int32_t> fa_aux;                   // msak::FA_WORDS, then the two 256-entry byte tables
+    DevBuf<uint32_t> fa_names;                // name offsets [m], then name ends [m]
+    DevBuf<unsigned long long> fa_rowtype;    // the type counts of every row
+    PinBuf<int32_t> h_fa;                     // ... the result words on the host, then the tables on their way up
+    int32_t fa_m = -1;                        // records of the last msa_upload_fasta that succeeded (msa_text_names), -1 none
+
     // profiling
     int prof_on = 0;  // 0 off, 1 every kernel group, 2 the similarity and pair passes only
     std::map<std::string, ProfEntry> prof;

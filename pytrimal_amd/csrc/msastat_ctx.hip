@@ -167,6 +167,7 @@ void msa_ctx_destroy(msa_ctx *c) {
     c->equal.release(); c->keep_res_d.release(); c->keep_seq_d.release(); c->hashes.release();
     c->h_i32.release(); c->h_f32.release(); c->h_u64.release(); c->h_u8.release(); c->h_raw.release();
     c->h_gapstage.release(); c->h_rowtot.release(); c->h_len.release(); c->h_colcnt.release();
+    c->fa_text.release(); c->fa_work.release(); c->fa_aux.release(); c->fa_names.release(); c->fa_rowtype.release(); c->h_fa.release();
     if (c->ev_gaps) (void)hipEventDestroy(c->ev_gaps);
     if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
     if (c->ev_digest) (void)hipEventDestroy(c->ev_digest);
@@ -497,6 +498,140 @@ int msa_attach_device(msa_ctx *c, const void *rowmajor_dev, int32_t m, int32_t n
                                    hipMemcpyDeviceToDevice, c->stream));
         c->raw = c->raw_own.p;
     }
+    return MSA_OK;
+}
+
+// ---- FASTA text -> the device layout (msastat_ingest.hip).  The text goes up as it is, one pageable copy (the runtime stages it;
+// against the context's pinned staging in 1 MB pieces, MSA_UPLOAD_DIRECT=0, it is the faster of the two: tools/from_files.py,
+// profiles/r07_from_files.jsonl), then two passes over it and one over the tiles' summaries; the host waits twice: for m and n
+// (the matrix is allocated by them), then for the failure key and the type counts.
+static void fasta_tables(const uint8_t *valid, uint8_t *out) {
+    // [0, 256): accepted residue bytes; [256, 512): pytrimal_amd.alignment._CLASS (1 letter, 2 DNA, 4 RNA, 8 degenerate)
+    for (int ch = 0; ch < 256; ++ch) {
+        out[ch] = valid ? (valid[ch] ? 1 : 0) : 1;
+        const int up = (ch >= 'a' && ch <= 'z') ? ch - 32 : ch;
+        uint8_t k = (ch == '-' || ch == '.' || ch == '?') ? 0 : 1;
+        if (up && std::strchr("AGCTN", up)) k |= 2;
+        if (up && std::strchr("AGCUN", up)) k |= 4;
+        if (up && std::strchr("RYKMSWBDHV", up)) k |= 8;
+        out[256 + ch] = k;
+    }
+}
+
+// detect_alignment_type's decision from the rows' verdicts (pytrimal_amd/alignment.py)
+static uint32_t fasta_seq_type(const int32_t *t) {
+    const int protein = t[0], g_rna = t[1], g_dna = t[2], ext_rna = t[3], ext_dna = t[4];
+    if (protein) return 4;
+    if (ext_dna != 0 && ext_dna > ext_rna) return 1 | 8;
+    if (ext_rna != 0 && ext_dna < ext_rna) return 2 | 8;
+    if (g_rna > g_dna) return 2;
+    return 1;
+}
+
+int msa_upload_fasta(msa_ctx *c, const uint8_t *text, int64_t len, const uint8_t *valid, msa_text_info *info, msa_err_detail *detail) {
+    if (!c || !info || len < 0 || (!text && len > 0) || len > INT32_MAX) return MSA_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->upload_pending) {
+        HIPCHK(c, hipEventSynchronize(c->ev_upload));
+        c->upload_pending = false;
+    }
+    // until the text has parsed the context holds an empty alignment
+    int rc = set_shape(c, 0, 0, 'X');
+    if (rc) return rc;
+    c->ld = 64;
+    c->raw = c->raw_own.p;
+    c->fa_m = -1;
+    c->paths[0] = MSA_PATH_UPLOAD_FASTA;
+    info->m = info->n = 0;
+    info->seq_type = 0;
+    if (len == 0) return MSA_OK;
+    const int L = (int)len;
+    const size_t nt = ((size_t)L + msak::FASTA_TILE - 1) / msak::FASTA_TILE;
+    const size_t sum_bytes = (nt * msak::fasta_tile_sum_bytes() + 255) & ~(size_t)255;
+    HIPCHK(c, c->fa_text.reserve(nt * msak::FASTA_TILE + 64));
+    HIPCHK(c, c->fa_work.reserve(sum_bytes + nt * msak::fasta_tile_state_bytes()));
+    HIPCHK(c, c->fa_aux.reserve(msak::FA_WORDS + 512 / 4));
+    HIPCHK(c, c->h_fa.reserve(msak::FA_WORDS + 512 / 4));
+    int32_t *h = c->h_fa.p;
+    uint8_t *tables_d = reinterpret_cast<uint8_t *>(c->fa_aux.p + msak::FA_WORDS);
+    fasta_tables(valid, reinterpret_cast<uint8_t *>(h + msak::FA_WORDS));
+    HIPCHK(c, hipMemcpyAsync(tables_d, h + msak::FA_WORDS, 512, hipMemcpyHostToDevice, c->stream));
+    if (c->tuning.upload_direct) {
+        HIPCHK(c, hipMemcpyAsync(c->fa_text.p, text, (size_t)L, hipMemcpyHostToDevice, c->stream));
+    } else {  // (MSA_UPLOAD_DIRECT=0, diagnostics: through the context's pinned staging in 1 MB pieces, each sent once it is packed)
+        HIPCHK(c, c->h_raw.reserve((size_t)L));
+        for (size_t at = 0; at < (size_t)L; at += (size_t)1 << 20) {
+            const size_t piece = std::min((size_t)L - at, (size_t)1 << 20);
+            std::memcpy(c->h_raw.p + at, text + at, piece);
+            HIPCHK(c, hipMemcpyAsync(c->fa_text.p + at, c->h_raw.p + at, piece, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    void *tilesum = c->fa_work.p, *tilestate = c->fa_work.p + sum_bytes;
+    msak::launch_fasta_parse(c->stream, c->fa_text.p, L, tilesum, tilestate, tables_d, c->fa_aux.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, c->fa_aux.p, msak::FA_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int m = h[msak::FA_M], n = h[msak::FA_N];
+    if (m == 0) return MSA_OK;
+    const int64_t ld = round_up(std::max(n, 1), 64);
+    HIPCHK(c, c->raw_own.reserve((size_t)m * ld + 256));
+    c->ld = ld;  // (zero_padding_for_shape clears m x c->ld bytes)
+    if ((rc = zero_padding_for_shape(c, m, n))) return rc;
+    HIPCHK(c, c->fa_names.reserve((size_t)2 * m));
+    HIPCHK(c, c->fa_rowtype.reserve((size_t)m));
+    HIPCHK(c, hipMemsetAsync(c->fa_rowtype.p, 0, (size_t)m * sizeof(unsigned long long), c->stream));
+    msak::FastaArgs a;
+    a.text = c->fa_text.p, a.len = L, a.tables = tables_d, a.tilestate = tilestate, a.aux = c->fa_aux.p;
+    a.raw = c->raw_own.p, a.ld = ld, a.name_off = c->fa_names.p, a.name_end = c->fa_names.p + m, a.rowtype = c->fa_rowtype.p;
+    msak::launch_fasta_scatter(c->stream, a);
+    msak::launch_fasta_type(c->stream, c->fa_rowtype.p, m, c->fa_aux.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, c->fa_aux.p, msak::FA_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fa_m = m;  // (the names are written whether the records parse or not)
+    info->m = m, info->n = n;
+    const uint32_t key = (uint32_t)h[msak::FA_ERRKEY];
+    if (key != 0xffffffffu) {  // the failure's (row, col, byte): the kernel of the tile that holds it, once more
+        msak::launch_fasta_detail(c->stream, a, key);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h, c->fa_aux.p, msak::FA_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (detail) detail->row = h[msak::FA_ROW], detail->col = h[msak::FA_COL], detail->byte = h[msak::FA_BYTE];
+        return h[msak::FA_KIND] ? h[msak::FA_KIND] : MSA_E_INVALID;
+    }
+    const uint32_t ty = n > 0 ? fasta_seq_type(h + msak::FA_TYPES) : 0;
+    if ((rc = set_shape(c, m, n, (ty & 4) ? 'X' : 'N'))) return rc;
+    c->ld = ld;
+    c->raw = c->raw_own.p;
+    info->seq_type = ty;
+    return MSA_OK;
+}
+
+int msa_text_names(msa_ctx *c, int64_t *name_off, int32_t *name_len) {
+    if (!c || c->fa_m < 0 || (c->fa_m > 0 && (!name_off || !name_len))) return MSA_E_INVALID;
+    const int m = c->fa_m;
+    if (m == 0) return MSA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint32_t> h((size_t)2 * m);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->fa_names.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; ++i) {
+        name_off[i] = h[i];
+        name_len[i] = (int32_t)(h[(size_t)m + i] - h[i]);
+    }
+    return MSA_OK;
+}
+
+int msa_download_rows(msa_ctx *c, uint8_t *rows, int64_t ld) {
+    if (!c || ld < c->n || (!rows && (int64_t)c->m * c->n > 0)) return MSA_E_INVALID;
+    if (c->m == 0 || c->n == 0) return MSA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->raw == c->h_raw.p) {  // rows read in place from the context's pinned staging (nothing in flight: see stage_rows_zero_copy)
+        for (int i = 0; i < c->m; ++i) std::memcpy(rows + (size_t)i * ld, c->raw + (size_t)i * c->ld, (size_t)c->n);
+        return MSA_OK;
+    }
+    HIPCHK(c, hipMemcpy2DAsync(rows, (size_t)ld, c->raw, (size_t)c->ld, (size_t)c->n, (size_t)c->m, hipMemcpyDeviceToHost, c->stream));
+    SYNC(c);
     return MSA_OK;
 }
 

@@ -250,4 +250,30 @@ int launch_cluster(hipStream_t s, const float *ident, int ldw, const int32_t *se
 void launch_rows_equal(hipStream_t s, const uint8_t *raw, int n, int64_t ld, const int32_t *pairs, int npairs,
                        int32_t *equal);
 
+// ---- msastat_ingest.hip: FASTA text in device memory -> residue matrix (msa_upload_fasta) ---------------------------------------
+constexpr int FASTA_TILE = 4096;  // bytes per workgroup of the two passes over the text
+// words of the parse's small result block (device): m, n, the first failure (byte offset, 0xffffffff = none) and its detail,
+// then the counts of the sequence-type rule (rows that are protein, plain RNA, plain DNA, degenerate RNA, degenerate DNA)
+enum { FA_M = 0, FA_N = 1, FA_ERRKEY = 2, FA_KIND = 3, FA_ROW = 4, FA_COL = 5, FA_BYTE = 6, FA_TYPES = 8, FA_WORDS = 16 };
+struct FastaArgs {
+    const uint8_t *text;      // len bytes, readable up to a multiple of FASTA_TILE
+    int len;
+    const uint8_t *tables;    // [256] accepted residue bytes, [256] letter classes (1 letter, 2 DNA, 4 RNA, 8 degenerate)
+    const void *tilestate;    // launch_fasta_parse's state at every tile start
+    int32_t *aux;             // FA_WORDS
+    uint8_t *raw;             // m x ld, the padding columns already zero
+    int64_t ld;
+    uint32_t *name_off, *name_end;   // [m]
+    unsigned long long *rowtype;     // [m], zeroed: the type counts of every row's first 100 letters
+};
+size_t fasta_tile_sum_bytes();
+size_t fasta_tile_state_bytes();
+// the tiles' summaries and the state at every tile start; m and n into aux (which it initialises)
+void launch_fasta_parse(hipStream_t s, const uint8_t *text, int len, void *tilesum, void *tilestate, const uint8_t *tables, int32_t *aux);
+// residues into raw, names, the first failure's offset, the per-row type counts
+void launch_fasta_scatter(hipStream_t s, const FastaArgs &a);
+void launch_fasta_type(hipStream_t s, const unsigned long long *rowtype, int m, int32_t *aux);
+// (code, row, col, byte) of the failure at byte offset `key` (what launch_fasta_scatter left in aux[FA_ERRKEY])
+void launch_fasta_detail(hipStream_t s, const FastaArgs &a, uint32_t key);
+
 }  // namespace msak

@@ -154,6 +154,11 @@ class BaseTrimmer:
                 matrix = _default_matrix("aa")
             else:
                 matrix = _default_matrix("ntdeg" if ty & 8 else "nt")
+        params, keep = self._params_for(matrix)
+        return alignment.names, dense, indet, params, keep
+
+    def _params_for(self, matrix):
+        """The parameter block of this trimmer for `matrix` and the objects it points into."""
         # the parameter block of this trimmer for this matrix: filled once, copied per alignment (trim_batch prepares
         # thousands of small alignments per call)
         # (keyed by the matrix AND by what configures the block -- the trimmer's state: an attribute written after the first
@@ -171,8 +176,18 @@ class BaseTrimmer:
             if len(cache) > 64:
                 cache.clear()
             entry = cache[key] = (bytes(template), (vhash, dist, matrix), matrix)
-        params = _lib.TrimParams.from_buffer_copy(entry[0])
-        return alignment.names, dense, indet, params, entry[1]
+        return _lib.TrimParams.from_buffer_copy(entry[0]), entry[1]
+
+    def _fasta_params(self, matrix=None):
+        """The three parameter blocks of `msa_trim_batch_fasta` -- amino acids (and an undetected type), nucleotides,
+        degenerate nucleotides: the matrices `_prepare` picks by type.  (`matrix`: None or a SimilarityMatrix; the caller
+        has checked it and the platform, as `_prepare` does.)"""
+        kinds = (matrix,) * 3 if matrix is not None else tuple(_default_matrix(k) for k in ("aa", "nt", "ntdeg"))
+        out, keep = (_lib.TrimParams * 3)(), []
+        for i, mx in enumerate(kinds):
+            out[i], k = self._params_for(mx)
+            keep.append(k)
+        return out, keep
 
     @staticmethod
     def _finish(names, dense, datatype, keep_res, keep_seq, info, only_gaps_rows, gaps_w, params):
