@@ -187,6 +187,36 @@ int msa_text_names(msa_ctx *ctx, int64_t *name_off, int32_t *name_len);
 /* the context's residue matrix -> host rows[m][ld] (ld >= n; the bytes behind n of a row are not written) */
 int msa_download_rows(msa_ctx *ctx, uint8_t *rows, int64_t ld);
 
+/* ---- trimmed alignment text composed on the device: what `Alignment.dump` / `dumps` (reference _trimal.pyx:604-731) get
+ *      from trimAl's FormatManager (format_handling.pxd:11-32) for the kept sequences and residues, without host rows.
+ *      The bytes are those of pytrimal_amd's host writers (alignment.py: _fast_fasta, _fast_clustal), corner cases included. --- */
+enum {
+    MSA_TEXT_FASTA = 0,     /* per kept sequence ">name\n", then its kept residues in lines of 60 */
+    MSA_TEXT_FASTA_M10 = 1, /* the same with every name cut to its first 10 bytes ("fasta_m10") */
+    MSA_TEXT_CLUSTAL = 2    /* header line, empty line, blocks of 60 kept columns: name padded to the longest kept name + 5 */
+};
+enum {
+    MSA_TEXT_F_NON_ASCII = 1u << 0, /* a kept name holds a byte >= 0x80: no text (the host writer counts characters there) */
+    MSA_TEXT_F_TOO_LONG = 1u << 1   /* the text would have 2^31 bytes or more: no text (the call returns MSA_E_INVALID) */
+};
+/* The length of that text from the closed form (replaces nothing in the reference, whose writer streams: it is what sizes
+ * the buffers): kept_m sequences with names of name_len[i] bytes (cut to 10 here for MSA_TEXT_FASTA_M10) and kept_n
+ * residues each.  Pure host function: needs no device.  MSA_E_INVALID for an unknown format or a negative count. */
+int msa_text_size(int32_t format, int32_t kept_m, int32_t kept_n, const int32_t *name_len, int64_t *out);
+/* Composes, on the context's stream, the text of the context's current alignment under keep_res[n] / keep_seq[m] (host
+ * memory, 0/1 bytes as msa_trim writes them; either nullable = keep all) into a device buffer of the context: `dumps`
+ * of the TrimmedAlignment with these masks (_trimal.pyx:604-731, 1085-1121).  names == NULL: the names of the last
+ * msa_upload_fasta on this context (its text is still on the device; MSA_E_INVALID when the current alignment is not
+ * that text's).  Otherwise names holds the bytes of the names of all m sequences, sequence i's at name_off[i], name_len[i]
+ * of them (host memory).  len_out: the text's length.  flags_out (nullable): MSA_TEXT_F_* -- with a flag set there is no
+ * text and *len_out is 0.  Works after any upload, with or without a trim in between.  Waits once for the stream (the
+ * kept counts and name lengths size the buffer); the composition itself is left in flight for msa_download_text. */
+int msa_emit_text(msa_ctx *ctx, int32_t format, const uint8_t *keep_res, const uint8_t *keep_seq, const uint8_t *names,
+                  const int64_t *name_off, const int32_t *name_len, int64_t *len_out, uint32_t *flags_out);
+/* the text of the last msa_emit_text -> out[cap] (host memory, cap >= its length); MSA_E_INVALID when there is none
+ * (no call, a flag, an upload since) */
+int msa_download_text(msa_ctx *ctx, uint8_t *out, int64_t cap);
+
 /* ---- whole trim: trimAlManager::clean_alignment (manager.pxd:88) as configured by the four
  *      `_configure_manager` methods (_trimal.pyx:1479-1497,1651-1659,1766-1769,1859-1862) ------ */
 enum {
@@ -271,6 +301,16 @@ int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *text
 int msa_batch_fasta_result(msa_batch *b, int32_t k, msa_text_info *info, const uint8_t **keep_res, const uint8_t **keep_seq,
                            const int64_t **name_off, const int32_t **name_len, const uint8_t **rows, msa_trim_info *tinfo,
                            msa_err_detail *detail);
+/* Files in, files out: msa_trim_batch_fasta whose workers, behind the trim of a text, compose its trimmed text in `format`
+ * (MSA_TEXT_*) under the masks the trim produced (msa_emit_text with the text's own names) and download it -- instead of
+ * the rows, or beside them with want_rows: `Alignment.load` + `trim` + `dump` (reference _trimal.pyx:517-601, 1334-1359,
+ * 604-731; format_handling.pxd:11-32) per file without host rows.  rc[k] is the parse's / the trim's as before; a text
+ * that raised a MSA_TEXT_F_* flag keeps rc[k] == MSA_OK and has no output.  msa_batch_fasta_text reads text k's output
+ * (owned by the batch object, valid until its next call): *text NULL and *len -1 when there is none -- the parse or the
+ * trim failed, the alignment is empty, a flag (in *flags), or the call was msa_trim_batch_fasta. */
+int msa_trim_batch_fasta_emit(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                              const msa_trim_params params_by_type[3], int32_t want_rows, int32_t format, int32_t *rc);
+int msa_batch_fasta_text(msa_batch *b, int32_t k, const uint8_t **text, int64_t *len, uint32_t *flags);
 /* the rows behind MSA_W_ONLY_GAPS_SEQUENCES of alignment k of the last call (as msa_trim_only_gaps_rows) */
 int msa_batch_only_gaps_rows(msa_batch *b, int32_t k, int32_t *rows, int32_t cap);
 const char *msa_batch_last_hip_error(const msa_batch *b, int32_t worker);

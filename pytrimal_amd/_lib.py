@@ -47,6 +47,7 @@ EXPORTS = [
     "msa_batch_only_gaps_rows", "msa_batch_last_hip_error", "msa_prof_get", "msa_prof_reset",
     "msa_prof_enable", "msa_debug_sim_launches", "msa_debug_last_paths", "msa_debug_switches_enabled", "msa_fasta_scan", "msa_fasta_fill", "msa_clustal_scan", "msa_clustal_fill",
     "msa_upload_fasta", "msa_text_names", "msa_download_rows", "msa_trim_batch_fasta", "msa_batch_fasta_result",
+    "msa_text_size", "msa_emit_text", "msa_download_text", "msa_trim_batch_fasta_emit", "msa_batch_fasta_text",
 ]
 
 
@@ -98,6 +99,30 @@ W_ONLY_GAPS_SEQUENCES, W_NO_COLUMNS_LEFT, W_UNDEFINED_IDENTITY = 1, 2, 4
 
 # the longest text msa_upload_fasta parses (32-bit offsets in its kernels)
 FASTA_MAX_BYTES = (1 << 31) - 1
+
+# the formats msa_emit_text composes on the device (MSA_TEXT_*), by the name `Alignment.dumps` knows them under
+TEXT_FORMATS = {"fasta": 0, "fasta_m10": 1, "clustal": 2}
+TEXT_F_NON_ASCII, TEXT_F_TOO_LONG = 1, 2
+
+
+def text_format_code(format):
+    """The MSA_TEXT_* code of a `dumps` format name (any letter case), or `ValueError` for one the device does not compose."""
+    code = TEXT_FORMATS.get(format.lower()) if isinstance(format, str) else None
+    if code is None:
+        raise ValueError(f"the device composes {sorted(TEXT_FORMATS)}, not {format!r}")
+    return code
+
+
+def text_size(format, name_lens, kept_n):
+    """Length in bytes of the text `dumps(format)` gives for sequences with names of `name_lens` bytes and `kept_n` residues
+    each (`msa_text_size`: the closed form that sizes the device writer's buffers; needs no device)."""
+    lens = np.ascontiguousarray(name_lens, dtype=np.int32)
+    out = ctypes.c_int64(0)
+    lib = load()
+    rc = lib.msa_text_size(text_format_code(format), lens.size, int(kept_n), ptr(lens) if lens.size else None, ctypes.byref(out))
+    if rc != OK:
+        raise ValueError(lib.msa_strerror(rc).decode())
+    return int(out.value)
 
 
 _lib = None
@@ -182,6 +207,12 @@ def load():
         pp = ctypes.POINTER(vp)
         L.msa_batch_fasta_result.argtypes = [vp, i32, ctypes.POINTER(TextInfo), pp, pp, pp, pp, pp, ctypes.POINTER(TrimInfo),
                                              ctypes.POINTER(ErrDetail)]
+        i64p, u32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint32)
+        L.msa_text_size.argtypes = [i32, i32, i32, vp, i64p]
+        L.msa_emit_text.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64p, u32p]
+        L.msa_download_text.argtypes = [vp, vp, ctypes.c_int64]
+        L.msa_trim_batch_fasta_emit.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp]
+        L.msa_batch_fasta_text.argtypes = [vp, i32, pp, i64p, u32p]
         L.msa_prof_get.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(f32), ctypes.POINTER(i32)]
         L.msa_prof_reset.argtypes = [vp]
         L.msa_prof_reset.restype = None
@@ -405,6 +436,43 @@ class Context:
         check(self.lib, self.h, self.lib.msa_download_rows(self.h, ptr(out), max(n, 1)))
         return out
 
+    def emit_text(self, format, keep_res=None, keep_seq=None, names=None):
+        """The text `TrimmedAlignment.dumps(format)` gives for this context's alignment under the masks `keep_res` [n] /
+        `keep_seq` [m] (None: keep all), composed on the device (`msa_emit_text` + `msa_download_text`), as bytes.  `format`:
+        "fasta", "fasta_m10" or "clustal".  `names`: the m sequences' names (bytes each); None: the names in the text of the
+        last `upload_fasta`.  Returns None when a kept name holds a non-ASCII byte: the host writer counts characters
+        there, and is the one to use.  A text of 2^31 bytes or more raises `MsaError` (E_INVALID)."""
+        code = text_format_code(format)
+        m, n = self.shape
+
+        def mask(x, count):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(x)
+            a = a.view(np.uint8) if a.dtype == np.bool_ else (a != 0).astype(np.uint8)
+            if a.shape != (count,):
+                raise ValueError("mask of the wrong length")
+            return a
+
+        res, seq = mask(keep_res, n), mask(keep_seq, m)
+        blob = off = lens = None
+        if names is not None:
+            names = [bytes(x) for x in names]
+            if len(names) != m:
+                raise ValueError(f"{len(names)} names for {m} sequences")
+            lens = np.array([len(x) for x in names], dtype=np.int32).reshape(m)
+            off = np.zeros(m, dtype=np.int64)
+            np.cumsum(lens[:-1], out=off[1:])
+            blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)  # (never empty: a null pointer means "the text's names")
+        size, flags = ctypes.c_int64(0), ctypes.c_uint32(0)
+        rc = self.lib.msa_emit_text(self.h, code, ptr(res), ptr(seq), ptr(blob), ptr(off), ptr(lens), ctypes.byref(size), ctypes.byref(flags))
+        if flags.value & TEXT_F_NON_ASCII:
+            return None
+        check(self.lib, self.h, rc)
+        out = np.empty(size.value, dtype=np.uint8)
+        check(self.lib, self.h, self.lib.msa_download_text(self.h, ptr(out), out.size))
+        return out.tobytes()
+
     def attach(self, dev_ptr, m, n, ld, indet):
         check(self.lib, self.h, self.lib.msa_attach_device(self.h, ctypes.c_void_p(dev_ptr), m, n, ld, indet))
         self.shape = (m, n)
@@ -625,11 +693,14 @@ class Batch:
                 out.append((flags[pos:pos + n], flags[pos + n:pos + n + m], infos[k], rc, rows))
         return out
 
-    def trim_fasta(self, texts, valid, params3, want_rows=False):
+    def trim_fasta(self, texts, valid, params3, want_rows=False, emit=None):
         """`texts`: FASTA texts (bytes-like, each < 2^31 bytes), `params3`: `TrimParams * 3` by type (msa_trim_batch_fasta)
         -> per text a dict: parse_rc, info (TextInfo), keep_res / keep_seq (bool, copies), name_off / name_len, rows
-        (uint8[m, n] with `want_rows`, else None), tinfo (TrimInfo), detail, rc, only_gaps_rows.  The interpreter lock is
-        released for the whole call."""
+        (uint8[m, n] with `want_rows`, else None), tinfo (TrimInfo), detail, rc, only_gaps_rows.  `emit`: "fasta",
+        "fasta_m10" or "clustal" -- the workers also compose the trimmed text on the device (msa_trim_batch_fasta_emit):
+        "text" (bytes, a copy; None where there is none: a failure, an empty alignment, a flag) and "text_flags"
+        (TEXT_F_*).  The interpreter lock is released for the whole call."""
+        emit_code = None if emit is None else text_format_code(emit)
         count = len(texts)
         if count == 0:
             return []
@@ -642,8 +713,12 @@ class Batch:
         with self._lock:
             if not self.h:
                 raise BatchClosed("the batch object is closed")
-            rc_all = self.lib.msa_trim_batch_fasta(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3, int(bool(want_rows)),
-                                                   ptr(rcs))
+            if emit_code is None:
+                rc_all = self.lib.msa_trim_batch_fasta(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3, int(bool(want_rows)),
+                                                       ptr(rcs))
+            else:
+                rc_all = self.lib.msa_trim_batch_fasta_emit(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3,
+                                                            int(bool(want_rows)), emit_code, ptr(rcs))
             if rc_all != OK and not rcs.any():
                 raise MsaError(rc_all, self.lib.msa_strerror(rc_all).decode())
             info, tinfo, det = TextInfo(), TrimInfo(), ErrDetail()
@@ -669,6 +744,11 @@ class Batch:
                     "rows": grab(p_rows, m * n, ctypes.c_uint8, np.uint8).reshape(m, n) if (want_rows and parsed and p_rows.value) else None,
                     "only_gaps_rows": [],
                 }
+                if emit_code is not None:
+                    p_text, t_len, t_flags = ctypes.c_void_p(), ctypes.c_int64(-1), ctypes.c_uint32(0)
+                    self.lib.msa_batch_fasta_text(self.h, k, ctypes.byref(p_text), ctypes.byref(t_len), ctypes.byref(t_flags))
+                    rec["text"] = ctypes.string_at(p_text.value, t_len.value) if t_len.value > 0 else (b"" if t_len.value == 0 else None)
+                    rec["text_flags"] = int(t_flags.value)
                 if parsed and tinfo.warnings & W_ONLY_GAPS_SEQUENCES:
                     cnt = self.lib.msa_batch_only_gaps_rows(self.h, k, None, 0)
                     if cnt > 0:

@@ -280,7 +280,8 @@ def _rebuild(alignment, keep_res, keep_seq, gap_stats=False):
 # Alignment.load + trim_batch, the C5 set 57 ms against 225), so there is no threshold below which small files take the host path.
 
 
-def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, threads=6, device=None):
+def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, threads=6, device=None, output=None,
+               output_format="fasta"):
     """Trim the alignments in `files` (paths or binary file objects) on this process's device.
 
     Returns and raises what ``trim_batch(trimmer, [Alignment.load(f, format) for f in files], matrix, shard=False,
@@ -289,14 +290,37 @@ def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, th
     workers (`threads` of them) with the matrix of its type.  Other formats, and texts the device does not parse (empty,
     longer than 2^31 - 1 bytes), go through `Alignment.load` and the row path in the same call.  Results come in input
     order; the failure of the first file (in input order) that does not load is raised before any trim failure.
+
+    `output`: a sequence as long as `files` of paths or binary file objects.  The call then also writes, for every file,
+    the bytes ``result.dump(output[k], output_format)`` writes for the `TrimmedAlignment` it returns (or would return
+    without `masks_only`), and returns what it returns without `output`.  For FASTA inputs and `output_format` "fasta",
+    "fasta_m10" or "clustal" the native workers compose the text on the device behind the trim, under the masks it
+    produced and with the names in the input text (`msa_trim_batch_fasta_emit`), and only the text comes back: with
+    `masks_only=True` no rows are downloaded -- files in, files out.  Everything else (inputs that went through
+    `Alignment.load`, a name with a non-ASCII byte, the other formats, a text of 2^31 bytes or more) is written by the
+    host writer from host rows, the same bytes.  A wrong length of `output` and a format `dumps` does not know are
+    `ValueError`s before any work; nothing is written unless every file loaded and every trim succeeded, and the outputs
+    are then written in input order.
     """
     from . import _lib
-    from .alignment import _VALID, _read_input, _sniff_format, _sniff_mapped
+    from .alignment import _M10_FORMATS, _VALID, _WRITERS, _read_input, _sniff_format, _sniff_mapped
     from .matrix import SimilarityMatrix
 
     files = list(files)
+    emit = None
+    if output is not None:
+        output = list(output)
+        if len(output) != len(files):
+            raise ValueError(f"`output` has {len(output)} entries for {len(files)} files")
+        fmt_out = output_format.lower()
+        short = fmt_out.endswith("_m10")
+        base = fmt_out[:-4] if short else fmt_out
+        if base not in _WRITERS or (short and base not in _M10_FORMATS):  # (what `dumps` checks, and its message)
+            raise ValueError(f"Could not recognize alignment format: {output_format!r}")
+        emit = fmt_out if fmt_out in _lib.TEXT_FORMATS else None
     if getattr(trimmer, "_platform", None) != "hip" or not (matrix is None or isinstance(matrix, SimilarityMatrix)):
         # (no device, or a matrix `trim` refuses: the composition itself, which raises what it raises where it raises it)
+        # (`output` needs a device trim first: this raises before anything could be written)
         return trim_batch(trimmer, [Alignment.load(f, format) for f in files], matrix, device=device, threads=threads, shard=False,
                           masks_only=masks_only)
     texts, failed = [], None  # (data, fmt) per file up to the first that cannot be read
@@ -327,7 +351,7 @@ def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, th
     done = {}
     if on_device:
         batch, outs = run(lambda b: b.trim_fasta([texts[k][0] for k in on_device], _VALID.view(np.uint8), params3,
-                                                  want_rows=not masks_only))
+                                                  want_rows=not masks_only, emit=emit))
         for k, rec in zip(on_device, outs):
             if rec["parse_rc"] not in (_lib.OK, _lib.E_BAD_RESIDUE, _lib.E_LENGTH_MISMATCH):
                 batch.check(rec["parse_rc"], rec["tinfo"])  # a device failure (HIP, memory) is raised, never hidden behind the host path
@@ -382,6 +406,26 @@ def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, th
         if ty is not None and rec["keep_res"].all() and rec["keep_seq"].all():
             t._detected_type = ty  # (nothing removed: the type the device detected is the result's)
         out.append(t)
+    if output is not None:  # every file loaded, every trim succeeded: the outputs, in input order
+        for k, (data, fmt) in enumerate(texts):
+            rec = done.get(k)
+            text = rec.get("text") if rec is not None else None
+            if text is None:  # the host writer, on the result object (or on what it would have been)
+                t = out[k]
+                if masks_only:
+                    res, seq = t
+                    if k in prepared:
+                        names, dense = prepared[k][0], prepared[k][1]
+                        t = TrimmedAlignment._from_parts(names, dense, loaded[k]._datatype, seq, res)
+                    else:  # parsed on the device and not composed there (a flag): its rows as the host reads them
+                        a = Alignment._from_text(data if isinstance(data, bytes) else bytes(data), files[k], format, fmt)
+                        t = TrimmedAlignment._from_parts(a._names, a._matrix, a._datatype, seq, res)
+                t.dump(output[k], output_format)
+            elif isinstance(output[k], (str, bytes, os.PathLike)):
+                with open(os.fspath(output[k]), "wb") as f:
+                    f.write(text)
+            else:
+                output[k].write(text)
     return out
 
 

@@ -54,6 +54,7 @@ struct msa_batch {
     const uint8_t *valid = nullptr;
     const msa_trim_params *params_by_type = nullptr;
     bool want_rows = false;
+    int emit_format = -1;  // msa_trim_batch_fasta_emit: the MSA_TEXT_* format the workers compose behind the trim, -1 none
     struct FastaResult {
         int parse_rc = MSA_OK;
         msa_text_info info{};
@@ -62,6 +63,9 @@ struct msa_batch {
         std::vector<uint8_t> keep_res, keep_seq, rows;
         std::vector<int64_t> name_off;
         std::vector<int32_t> name_len;
+        std::unique_ptr<uint8_t[]> text;  // the composed text (not value-initialised: every byte comes from the download)
+        int64_t text_len = -1;            // -1: none
+        uint32_t text_flags = 0;          // MSA_TEXT_F_*
     };
     std::vector<FastaResult> fasta;
 };
@@ -741,6 +745,17 @@ int fasta_item(msa_batch *b, msa_ctx *c, int32_t k) {
             r.rows.resize((size_t)m * n);
             rc = msa_download_rows(c, r.rows.data(), n);
         }
+        if (rc == MSA_OK && b->emit_format >= 0) {  // the trimmed text, composed under the masks of this trim with the text's own names
+            int64_t len = 0;
+            const int erc = msa_emit_text(c, b->emit_format, r.keep_res.data(), r.keep_seq.data(), nullptr, nullptr, nullptr, &len, &r.text_flags);
+            if (erc == MSA_OK && !r.text_flags) {
+                r.text.reset(new uint8_t[(size_t)std::max<int64_t>(len, 1)]);
+                if ((rc = msa_download_text(c, r.text.get(), len)) == MSA_OK) r.text_len = len;
+                else r.text.reset();
+            } else if (erc != MSA_OK && !(r.text_flags & MSA_TEXT_F_TOO_LONG)) {
+                rc = erc;  // (a text too long for the device is the caller's to write: the flag says so, the trim stands)
+            }
+        }
     }
     if (rc == MSA_OK && m > 0) {
         r.name_off.resize((size_t)m);
@@ -932,8 +947,8 @@ int msa_trim_batch(msa_batch *b, int32_t count, const uint8_t *const *data, cons
     return MSA_OK;
 }
 
-int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
-                         const msa_trim_params params_by_type[3], int32_t want_rows, int32_t *rc) {
+static int trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                            const msa_trim_params params_by_type[3], int32_t want_rows, int32_t format, int32_t *rc) {
     if (!b || count < 0 || (count > 0 && (!texts || !lens || !params_by_type || !rc))) return MSA_E_INVALID;
     if (count == 0) return MSA_OK;
     {
@@ -942,11 +957,13 @@ int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *text
         b->in_call = true;
         b->count = count;
         b->texts = texts, b->lens = lens, b->valid = valid, b->params_by_type = params_by_type, b->want_rows = want_rows != 0;
+        b->emit_format = format;
         b->info = nullptr, b->rc = rc;
         b->order.resize(count);
         for (int32_t k = 0; k < count; ++k) b->order[k] = k;
         std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return lens[x] > lens[y]; });  // largest first
-        b->fasta.assign(count, msa_batch::FastaResult());
+        b->fasta.clear();
+        b->fasta.resize((size_t)count);
         b->only_gaps.assign(count, {});
         for (int32_t k = 0; k < count; ++k) rc[k] = MSA_OK;
         b->next.store(0);
@@ -962,6 +979,26 @@ int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *text
     }
     for (int32_t k = 0; k < count; ++k)
         if (rc[k] != MSA_OK) return rc[k];
+    return MSA_OK;
+}
+
+int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                         const msa_trim_params params_by_type[3], int32_t want_rows, int32_t *rc) {
+    return trim_batch_fasta(b, count, texts, lens, valid, params_by_type, want_rows, -1, rc);
+}
+
+int msa_trim_batch_fasta_emit(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
+                              const msa_trim_params params_by_type[3], int32_t want_rows, int32_t format, int32_t *rc) {
+    if (format < MSA_TEXT_FASTA || format > MSA_TEXT_CLUSTAL) return MSA_E_INVALID;
+    return trim_batch_fasta(b, count, texts, lens, valid, params_by_type, want_rows, format, rc);
+}
+
+int msa_batch_fasta_text(msa_batch *b, int32_t k, const uint8_t **text, int64_t *len, uint32_t *flags) {
+    if (!b || k < 0 || k >= (int32_t)b->fasta.size()) return MSA_E_INVALID;
+    const msa_batch::FastaResult &r = b->fasta[k];
+    if (text) *text = r.text_len >= 0 ? r.text.get() : nullptr;
+    if (len) *len = r.text_len;
+    if (flags) *flags = r.text_flags;
     return MSA_OK;
 }
 

@@ -1,6 +1,7 @@
 // msastat_ctx.h -- internal: the context behind include/msastat.h's opaque msa_ctx, its helpers, and the functions the
 // translation units of the C-ABI shim share (msastat_ctx.hip: context, uploads, instrumentation; msastat_stats.hip: one
-// entry point per statistic; msastat_trim.hip: msa_trim and its two pipelines; msastat_batch.hip: msa_trim_batch).
+// entry point per statistic; msastat_trim.hip: msa_trim and its two pipelines; msastat_batch.hip: msa_trim_batch;
+// msastat_emit.hip: msa_emit_text with its kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -231,6 +232,12 @@ struct msa_ctx {
     DevBuf<unsigned long long> fa_rowtype;    // the type counts of every row
     PinBuf<int32_t> h_fa;                     // ... the result words on the host, then the tables on their way up
     int32_t fa_m = -1;                        // records of the last msa_upload_fasta that succeeded (msa_text_names), -1 none
+
+    // msa_emit_text (msastat_emit.hip): the call's inputs (caller's names, masks) on their way up and on the device, the
+    // index pass's lists (kept columns, kept rows, their name lengths and record starts), the composed text
+    PinBuf<uint8_t> h_em;
+    DevBuf<uint8_t> em_in, em_idx, em_out;
+    int64_t em_len = -1;                      // length of the text in em_out, -1 none (every upload resets it: invalidate)
 
     // profiling
     int prof_on = 0;  // 0 off, 1 every kernel group, 2 the similarity and pair passes only

@@ -58,6 +58,7 @@ void invalidate(msa_ctx *c) {
     c->flags_dirty = false;
     c->colcnt_staged = false;
     c->ov_valid = c->ov_colcnt = false;
+    c->em_len = -1;  // (msa_download_text: the composed text was another alignment's)
 }
 
 // the state block of the current alignment, zeroed once (one memset for the flags and both count vectors)
@@ -168,6 +169,7 @@ void msa_ctx_destroy(msa_ctx *c) {
     c->h_i32.release(); c->h_f32.release(); c->h_u64.release(); c->h_u8.release(); c->h_raw.release();
     c->h_gapstage.release(); c->h_rowtot.release(); c->h_len.release(); c->h_colcnt.release();
     c->fa_text.release(); c->fa_work.release(); c->fa_aux.release(); c->fa_names.release(); c->fa_rowtype.release(); c->h_fa.release();
+    c->h_em.release(); c->em_in.release(); c->em_idx.release(); c->em_out.release();
     if (c->ev_gaps) (void)hipEventDestroy(c->ev_gaps);
     if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
     if (c->ev_digest) (void)hipEventDestroy(c->ev_digest);
