@@ -10,7 +10,9 @@ BEFORE the first call into this module.  The torch wheel bundles its own ``libam
 the system runtime is mapped first (through this library), torch later finds no GPU.
 """
 import collections
+import contextlib
 import ctypes
+import dataclasses
 import os
 import threading
 
@@ -342,16 +344,32 @@ def check(lib, ctx, rc, detail=None):
     raise MsaError(rc, msg, detail)
 
 
+def default_device(wrap=False):
+    """The device index a caller that names none gets: PYTRIMAL_AMD_DEVICE, else a launcher's LOCAL_RANK, else 0.  `wrap`:
+    modulo the number of visible devices (`Context`, `Batch`: more ranks than devices share them)."""
+    device = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    n = load().msa_device_count() if wrap else 0
+    return device % n if n > 0 else device
+
+
+def _only_gaps_rows(fetch, *trim):
+    """The rows behind `W_ONLY_GAPS_SEQUENCES`.  `fetch(*trim, rows, capacity)`: `msa_trim_only_gaps_rows` of a context or
+    `msa_batch_only_gaps_rows` of a batch object and an index, which fills what fits and returns how many there are."""
+    n = fetch(*trim, None, 0)
+    if n <= 0:
+        return []
+    rows = np.empty(n, dtype=np.int32)
+    fetch(*trim, ptr(rows), n)
+    return rows.tolist()
+
+
 class Context:
     """One `msa_ctx`: device buffers + a HIP stream.  Not shared between threads."""
 
     def __init__(self, device=None):
         self.lib = load()
         if device is None:
-            device = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-            n = self.lib.msa_device_count()
-            if n > 0:
-                device %= n
+            device = default_device(wrap=True)
         h = ctypes.c_void_p()
         rc = self.lib.msa_ctx_create(int(device), ctypes.byref(h))
         if rc != OK:
@@ -545,12 +563,7 @@ class Context:
 
     def only_gaps_rows(self):
         """The sequences the last `trim` removed because it left them with gaps only."""
-        n = self.lib.msa_trim_only_gaps_rows(self.h, None, 0)
-        if n <= 0:
-            return []
-        rows = np.empty(n, dtype=np.int32)
-        self.lib.msa_trim_only_gaps_rows(self.h, ptr(rows), n)
-        return [int(r) for r in rows]
+        return _only_gaps_rows(self.lib.msa_trim_only_gaps_rows, self.h)
 
     # --- instrumentation ---
     def prof_enable(self, on=True):
@@ -602,6 +615,32 @@ class _BatchResults(list):
     packed = None
 
 
+@dataclasses.dataclass
+class TrimRecord:
+    """What one alignment of a batch call gave, whichever way it went: a text of `Batch.trim_fasta`, or (`trim_files`) an
+    alignment of the row path.  The masks of a text are copies (bool; empty when it did not parse)."""
+    keep_res: np.ndarray = None   # (None: an empty alignment, which never reaches the device)
+    keep_seq: np.ndarray = None
+    tinfo: TrimInfo = None
+    rc: int = OK
+    only_gaps_rows: list = None
+    rows: np.ndarray = None       # uint8[m, n]; a text's with `want_rows`
+    # a text
+    parse_rc: int = OK
+    info: TextInfo = None
+    detail: ErrDetail = None
+    name_off: np.ndarray = None   # int64[m], int32[m]: the records' names in the text
+    name_len: np.ndarray = None
+    text: bytes = None            # with `emit`: the composed text (a copy); None where there is none: a failure, an empty alignment, a flag
+    text_flags: int = 0           # TEXT_F_*
+    # what `trim_files` adds
+    names: list = None
+    datatype: int = 0
+    params: TrimParams = None
+    batch: "Batch" = None         # the object that trimmed it (`check`)
+    data: object = None           # the text itself: the mapping lives as long as the record
+
+
 class Batch:
     """One `msa_batch`: native worker threads, each with its own device context, that trim the alignments of a call side
     by side (`msa_trim_batch`: the reference's `ThreadPool.map(trimmer.trim, ...)` without the interpreter)."""
@@ -609,10 +648,7 @@ class Batch:
     def __init__(self, device=None, workers=6):
         self.lib = load()
         if device is None:
-            device = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-            n = self.lib.msa_device_count()
-            if n > 0:
-                device %= n
+            device = default_device(wrap=True)
         h = ctypes.c_void_p()
         rc = self.lib.msa_batch_create(int(device), int(workers), ctypes.byref(h))
         if rc != OK:
@@ -636,6 +672,19 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+    @contextlib.contextmanager
+    def _called(self, call, rcs, *args):
+        """One native call `call(handle, *args, rcs)` of this object, under its lock: `BatchClosed` for a closed object,
+        `MsaError` when the call itself was refused (no alignment was looked at).  The body reads the call's results: they
+        belong to the object until its next call, so the lock is kept until the body is through."""
+        with self._lock:
+            if not self.h:
+                raise BatchClosed("the batch object is closed")
+            rc_all = call(self.h, *args, ptr(rcs))
+            if rc_all != OK and not rcs.any():
+                raise MsaError(rc_all, self.lib.msa_strerror(rc_all).decode())
+            yield
 
     def trim(self, items):
         """`items`: [(matrix uint8[m, n] (C-contiguous rows, any row stride), indet, TrimParams), ...] ->
@@ -674,32 +723,19 @@ class Batch:
         rcs = np.zeros(count, dtype=np.int32)
         out = _BatchResults()
         out.packed = masks  # [residues mask, sequences mask] of every item, side by side (what trim_batch's gather sends)
-        with self._lock:
-            if not self.h:
-                raise BatchClosed("the batch object is closed")
-            rc_all = self.lib.msa_trim_batch(self.h, count, ptr(data), ptr(ms), ptr(ns), ptr(lds), ptr(indets), params, ptr(kres), ptr(kseq),
-                                             infos, ptr(rcs))
-            if rc_all != OK and not rcs.any():  # the call itself was refused: no alignment was looked at
-                raise MsaError(rc_all, self.lib.msa_strerror(rc_all).decode())
+        with self._called(self.lib.msa_trim_batch, rcs, count, ptr(data), ptr(ms), ptr(ns), ptr(lds), ptr(indets), params, ptr(kres),
+                          ptr(kseq), infos):
             flags = masks.view(np.bool_)  # (the library writes 0 / 1: the same bytes as booleans, no copy per alignment)
             for k, pos, n, m, rc in zip(range(count), starts.tolist(), ns.tolist(), ms.tolist(), rcs.tolist()):
-                rows = []
-                if infos[k].warnings & W_ONLY_GAPS_SEQUENCES:
-                    cnt = self.lib.msa_batch_only_gaps_rows(self.h, k, None, 0)
-                    if cnt > 0:
-                        buf = np.empty(cnt, dtype=np.int32)
-                        self.lib.msa_batch_only_gaps_rows(self.h, k, ptr(buf), cnt)
-                        rows = [int(r) for r in buf]
+                rows = _only_gaps_rows(self.lib.msa_batch_only_gaps_rows, self.h, k) if infos[k].warnings & W_ONLY_GAPS_SEQUENCES else []
                 out.append((flags[pos:pos + n], flags[pos + n:pos + n + m], infos[k], rc, rows))
         return out
 
     def trim_fasta(self, texts, valid, params3, want_rows=False, emit=None):
         """`texts`: FASTA texts (bytes-like, each < 2^31 bytes), `params3`: `TrimParams * 3` by type (msa_trim_batch_fasta)
-        -> per text a dict: parse_rc, info (TextInfo), keep_res / keep_seq (bool, copies), name_off / name_len, rows
-        (uint8[m, n] with `want_rows`, else None), tinfo (TrimInfo), detail, rc, only_gaps_rows.  `emit`: "fasta",
-        "fasta_m10" or "clustal" -- the workers also compose the trimmed text on the device (msa_trim_batch_fasta_emit):
-        "text" (bytes, a copy; None where there is none: a failure, an empty alignment, a flag) and "text_flags"
-        (TEXT_F_*).  The interpreter lock is released for the whole call."""
+        -> per text a `TrimRecord` (what `trim_files` adds left empty; `rows` with `want_rows`).  `emit`: "fasta", "fasta_m10"
+        or "clustal" -- the workers also compose the trimmed text on the device (msa_trim_batch_fasta_emit): `text` and
+        `text_flags`.  The interpreter lock is released for the whole call."""
         emit_code = None if emit is None else text_format_code(emit)
         count = len(texts)
         if count == 0:
@@ -709,52 +745,38 @@ class Batch:
         lens = np.array([b.size for b in bufs], dtype=np.int64)
         valid = np.ascontiguousarray(valid, dtype=np.uint8)
         rcs = np.zeros(count, dtype=np.int32)
+        args = (count, ptr(addr), ptr(lens), ptr(valid), params3, int(bool(want_rows)))
+        call = self.lib.msa_trim_batch_fasta if emit_code is None else self.lib.msa_trim_batch_fasta_emit
         out = []
-        with self._lock:
-            if not self.h:
-                raise BatchClosed("the batch object is closed")
-            if emit_code is None:
-                rc_all = self.lib.msa_trim_batch_fasta(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3, int(bool(want_rows)),
-                                                       ptr(rcs))
-            else:
-                rc_all = self.lib.msa_trim_batch_fasta_emit(self.h, count, ptr(addr), ptr(lens), ptr(valid), params3,
-                                                            int(bool(want_rows)), emit_code, ptr(rcs))
-            if rc_all != OK and not rcs.any():
-                raise MsaError(rc_all, self.lib.msa_strerror(rc_all).decode())
+        with self._called(call, rcs, *(args if emit_code is None else args + (emit_code,))):
             info, tinfo, det = TextInfo(), TrimInfo(), ErrDetail()
             p_res, p_seq, p_off, p_len, p_rows = (ctypes.c_void_p() for _ in range(5))
+            p_text, t_len, t_flags = ctypes.c_void_p(), ctypes.c_int64(-1), ctypes.c_uint32(0)
+
+            def grab(p, count, ctype, dtype):
+                if not p.value or count == 0:
+                    return np.zeros(count, dtype=dtype)
+                return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
+
             for k in range(count):
                 parse_rc = self.lib.msa_batch_fasta_result(self.h, k, ctypes.byref(info), ctypes.byref(p_res), ctypes.byref(p_seq),
                                                            ctypes.byref(p_off), ctypes.byref(p_len), ctypes.byref(p_rows),
                                                            ctypes.byref(tinfo), ctypes.byref(det))
                 m, n = info.m, info.n
-
-                def grab(p, count, ctype, dtype):
-                    if not p.value or count == 0:
-                        return np.zeros(count, dtype=dtype)
-                    return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
-
                 parsed = parse_rc == OK
-                rec = {
-                    "parse_rc": parse_rc, "info": TextInfo(m, n, info.seq_type), "rc": int(rcs[k]),
-                    "tinfo": TrimInfo.from_buffer_copy(tinfo), "detail": ErrDetail.from_buffer_copy(det),
-                    "keep_res": grab(p_res, n if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
-                    "keep_seq": grab(p_seq, m if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
-                    "name_off": grab(p_off, m, ctypes.c_int64, np.int64), "name_len": grab(p_len, m, ctypes.c_int32, np.int32),
-                    "rows": grab(p_rows, m * n, ctypes.c_uint8, np.uint8).reshape(m, n) if (want_rows and parsed and p_rows.value) else None,
-                    "only_gaps_rows": [],
-                }
+                rec = TrimRecord(
+                    parse_rc=parse_rc, info=TextInfo(m, n, info.seq_type), rc=int(rcs[k]),
+                    tinfo=TrimInfo.from_buffer_copy(tinfo), detail=ErrDetail.from_buffer_copy(det),
+                    keep_res=grab(p_res, n if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
+                    keep_seq=grab(p_seq, m if parsed else 0, ctypes.c_uint8, np.uint8).view(np.bool_),
+                    name_off=grab(p_off, m, ctypes.c_int64, np.int64), name_len=grab(p_len, m, ctypes.c_int32, np.int32),
+                    rows=grab(p_rows, m * n, ctypes.c_uint8, np.uint8).reshape(m, n) if (want_rows and parsed and p_rows.value) else None,
+                    only_gaps_rows=(_only_gaps_rows(self.lib.msa_batch_only_gaps_rows, self.h, k)
+                                    if parsed and tinfo.warnings & W_ONLY_GAPS_SEQUENCES else []))
                 if emit_code is not None:
-                    p_text, t_len, t_flags = ctypes.c_void_p(), ctypes.c_int64(-1), ctypes.c_uint32(0)
                     self.lib.msa_batch_fasta_text(self.h, k, ctypes.byref(p_text), ctypes.byref(t_len), ctypes.byref(t_flags))
-                    rec["text"] = ctypes.string_at(p_text.value, t_len.value) if t_len.value > 0 else (b"" if t_len.value == 0 else None)
-                    rec["text_flags"] = int(t_flags.value)
-                if parsed and tinfo.warnings & W_ONLY_GAPS_SEQUENCES:
-                    cnt = self.lib.msa_batch_only_gaps_rows(self.h, k, None, 0)
-                    if cnt > 0:
-                        buf = np.empty(cnt, dtype=np.int32)
-                        self.lib.msa_batch_only_gaps_rows(self.h, k, ptr(buf), cnt)
-                        rec["only_gaps_rows"] = [int(r) for r in buf]
+                    rec.text = ctypes.string_at(p_text.value, t_len.value) if t_len.value > 0 else (b"" if t_len.value == 0 else None)
+                    rec.text_flags = int(t_flags.value)
                 out.append(rec)
         return out
 

@@ -265,12 +265,7 @@ class Alignment:
 
     def dump(self, file, format="fasta"):
         """Dump the alignment to a path or a binary file-like object."""
-        text = self.dumps(format).encode("ascii")
-        if isinstance(file, (str, bytes, os.PathLike)):
-            with open(os.fspath(file), "wb") as f:
-                f.write(text)
-        else:
-            file.write(text)
+        _write_bytes(file, self.dumps(format).encode("ascii"))
 
     def dumps(self, format="fasta", encoding="utf-8"):
         """Dump the alignment to a string in one of the formats of the reference's writer
@@ -424,6 +419,15 @@ class TrimmedAlignment(Alignment):
 
 
 # --- minimal readers --------------------------------------------------------------------------
+
+def _write_bytes(file, data):
+    """`data` into a path or a binary file-like object."""
+    if isinstance(file, (str, bytes, os.PathLike)):
+        with open(os.fspath(file), "wb") as f:
+            f.write(data)
+    else:
+        file.write(data)
+
 
 def _read_input(file, format, mapped=False):
     """The bytes of a path or a binary file-like object, with `Alignment.load`'s checks and messages.  `mapped`: a path to a

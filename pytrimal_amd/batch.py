@@ -19,8 +19,11 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .trimmer import _raise_warnings
-from .alignment import Alignment, TrimmedAlignment
+from . import _lib  # (the module alone: the HIP library is loaded on first use)
+from .trimmer import BaseTrimmer, _raise_warnings, computes_gap_stats, type_index
+from .alignment import (_M10_FORMATS, _VALID, _WRITERS, Alignment, TrimmedAlignment, _read_input, _sniff_format, _sniff_mapped,
+                        _write_bytes)
+from .matrix import SimilarityMatrix
 
 # One native batch object (worker threads + their device contexts: O(m^2) buffers each) per (device, workers), kept
 # between calls, closed at exit, rebuilt in a child process (worker threads do not survive a fork).
@@ -49,8 +52,6 @@ def close_batches():
 
 
 def _native_batch(device_index, workers):
-    from . import _lib
-
     global _BATCHES_PID
     with _BATCHES_LOCK:
         if _BATCHES_PID != os.getpid():
@@ -65,6 +66,51 @@ def _native_batch(device_index, workers):
         return b
 
 
+def _device_index(device):
+    return device.index if isinstance(device, torch.device) and device.index is not None else _lib.default_device()
+
+
+def _on_native_batch(index, threads, call):
+    """`call(batch)` on device `index`'s native batch object of `threads` workers -> (batch, what it returned); again when
+    another thread (asking for another worker count) replaced and closed the object in between."""
+    for attempt in range(3):
+        batch = _native_batch(index, max(1, min(int(threads), 64)))
+        try:
+            return batch, call(batch)
+        except _lib.BatchClosed:
+            if attempt == 2:
+                raise
+
+
+def _trim_rows(trimmer, alignments, matrix, device, threads):
+    """The row path: `_prepare` every alignment, one `Batch.trim` over those that are not empty -> (what `_prepare` gave, per
+    alignment `Batch.trim`'s tuple or None, the batch object, the call's packed masks when every alignment took part in it)."""
+    prepared = [trimmer._prepare(a, matrix) for a in alignments]
+    _mark("prepare")
+    todo = [k for k, p in enumerate(prepared) if p[1].shape[0] and p[1].shape[1]]
+    outs, batch, packed = [None] * len(prepared), None, None
+    if todo:
+        items = [prepared[k][1:4] for k in todo]
+        batch, got = _on_native_batch(_device_index(device), threads, lambda b: b.trim(items))
+        for k, out in zip(todo, got):
+            outs[k] = out
+        if len(todo) == len(prepared):  # (no empty alignment in between: the library's mask vector IS the gather's payload)
+            packed = getattr(got, "packed", None)
+    return prepared, outs, batch, packed
+
+
+def _result(trimmer, names, dense, datatype, res, seq, info, rows, params, masks_only):
+    """The tail of a trim: (residues mask, sequences mask, `TrimmedAlignment`) -- with `masks_only` the warnings are raised and
+    the third is None.  `res` None: an empty alignment, which never reaches the device and keeps everything."""
+    if res is None:
+        res, seq, info, rows = np.ones(dense.shape[1], dtype=bool), np.ones(dense.shape[0], dtype=bool), None, None
+    if not masks_only:
+        return res, seq, trimmer._finish(names, dense, datatype, res, seq, info, rows, None, params)
+    if info is not None and info.warnings:
+        _raise_warnings(info, names, rows)
+    return res, seq, None
+
+
 def shard_indices(n_items, world_size, rank):
     """Static round-robin: item i belongs to rank i % world_size."""
     return list(range(rank, n_items, world_size))
@@ -77,15 +123,6 @@ def broadcast_trimmer(trimmer, src=0, group=None):
     box = [trimmer if dist.get_rank(group) == src else None]
     dist.broadcast_object_list(box, src=src, group=group)
     return box[0]
-
-
-def _pack_masks(results):
-    """[(keep_res bool[n], keep_seq bool[m]), ...] -> one uint8 vector."""
-    parts = []
-    for res, seq in results:
-        parts.append(np.asarray(res, dtype=np.uint8))
-        parts.append(np.asarray(seq, dtype=np.uint8))
-    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
 
 
 def trim_batch(trimmer, alignments, matrix=None, *, group=None, device=None, trim_fn=None, threads=6, shard=True,
@@ -124,45 +161,14 @@ def trim_batch(trimmer, alignments, matrix=None, *, group=None, device=None, tri
                 res, seq = t.residues_mask, t.sequences_mask
             local.append((np.asarray(res, dtype=bool), np.asarray(seq, dtype=bool), t))
     else:
-        from . import _lib
-
-        prepared = [trimmer._prepare(alignments[i], matrix) for i in mine]
-        _mark("prepare")
-        index = device.index if isinstance(device, torch.device) and device.index is not None else None
-        if index is None:
-            index = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-        todo = [k for k, (_, dense, _, _, _) in enumerate(prepared) if dense.shape[0] and dense.shape[1]]
-        results = {}
-        packed_masks = None
-        if todo:
-            items = [(prepared[k][1], prepared[k][2], prepared[k][3]) for k in todo]
-            for attempt in range(3):
-                batch = _native_batch(index, max(1, min(int(threads), 64)))
-                try:
-                    outs = batch.trim(items)
-                    break
-                except _lib.BatchClosed:  # a thread asking for another worker count replaced the device's batch object
-                    if attempt == 2:
-                        raise
-            for k, out in zip(todo, outs):
-                if out[3] != _lib.OK:
-                    batch.check(out[3], out[2])
-                results[k] = out
-            if len(todo) == len(prepared):  # (no empty alignment in between: the library's mask vector IS the gather's payload)
-                packed_masks = getattr(outs, "packed", None)
+        prepared, outs, batch, packed_masks = _trim_rows(trimmer, [alignments[i] for i in mine], matrix, device, threads)
+        for out in outs:
+            if out is not None and out[3] != _lib.OK:
+                batch.check(out[3], out[2])
         local = []
-        for k, (names, dense, indet, params, _keep) in enumerate(prepared):
-            if k in results:
-                res, seq, info, _, rows = results[k]
-            else:  # an empty alignment never reaches the device
-                res, seq, info, rows = np.ones(dense.shape[1], dtype=bool), np.ones(dense.shape[0], dtype=bool), None, None
-            if masks_only:
-                if info is not None and info.warnings:
-                    _raise_warnings(info, names, rows)
-                t = None
-            else:
-                t = trimmer._finish(names, dense, alignments[mine[k]]._datatype, res, seq, info, rows, None, params)
-            local.append((res, seq, t))
+        for i, (names, dense, _, params, _keep), out in zip(mine, prepared, outs):
+            res, seq, info, _, rows = out or (None,) * 5
+            local.append(_result(trimmer, names, dense, alignments[i]._datatype, res, seq, info, rows, params, masks_only))
     _mark("native batch")
     collect = distributed and (world > 1 or force_collectives)
     if masks_only and not collect:
@@ -170,7 +176,7 @@ def trim_batch(trimmer, alignments, matrix=None, *, group=None, device=None, tri
     if not collect:
         # (what the workers produced, as it is: rebuilding 64 results from their masks in the calling thread was a serial
         # tail of ~4 ms behind a 35 ms batch)
-        return [t if isinstance(t, TrimmedAlignment) else _rebuild(alignments[i], r, s, _gap_stats(trimmer)) for i, (r, s, t) in zip(mine, local)]
+        return [t if isinstance(t, TrimmedAlignment) else _rebuild(alignments[i], r, s, trimmer) for i, (r, s, t) in zip(mine, local)]
     mine_trimmed = {i: t for i, (_, _, t) in zip(mine, local)}
 
     # every rank knows every shape, so shard payload sizes are known without a size exchange
@@ -216,7 +222,7 @@ def trim_batch(trimmer, alignments, matrix=None, *, group=None, device=None, tri
                 out[i] = (res, seq)
                 continue
             t = mine_trimmed.get(i) if r == rank else None
-            out[i] = t if isinstance(t, TrimmedAlignment) else _rebuild(alignments[i], res, seq, _gap_stats(trimmer))
+            out[i] = t if isinstance(t, TrimmedAlignment) else _rebuild(alignments[i], res, seq, trimmer)
     _mark("D2H + unpack")
     return out
 
@@ -259,18 +265,13 @@ def _mark(what):
         _TRACE.append((what, time.perf_counter()))
 
 
-def _gap_stats(trimmer):
-    """Does this trimmer compute gap statistics (what its results' `terminal_only` shares with the source alignment)?"""
-    from .trimmer import AutomaticTrimmer, ManualTrimmer
-
-    return isinstance(trimmer, ManualTrimmer) or (isinstance(trimmer, AutomaticTrimmer) and trimmer.method != "noduplicateseqs")
-
-
-def _rebuild(alignment, keep_res, keep_seq, gap_stats=False):
+def _rebuild(alignment, keep_res, keep_seq, trimmer):
     dense = alignment._dense()
     whole = len(alignment._seq_idx) == len(alignment._names)  # (every sequence visible: the list of names is shared, not copied)
     out = TrimmedAlignment._from_parts(alignment._names if whole else alignment.names, dense, alignment._datatype, keep_seq, keep_res)
-    out._gap_stats = gap_stats  # (what `terminal_only` counts over: trimmer._finish)
+    # (what `terminal_only` counts over, asked of the trimmer's parameter block as `trimmer._finish` asks it for the results a
+    # trim builds itself; a `trim_fn` may come without a trimmer)
+    out._gap_stats = isinstance(trimmer, BaseTrimmer) and computes_gap_stats(trimmer._template())
     return out
 
 
@@ -302,143 +303,117 @@ def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, th
     `ValueError`s before any work; nothing is written unless every file loaded and every trim succeeded, and the outputs
     are then written in input order.
     """
-    from . import _lib
-    from .alignment import _M10_FORMATS, _VALID, _WRITERS, _read_input, _sniff_format, _sniff_mapped
-    from .matrix import SimilarityMatrix
-
     files = list(files)
-    emit = None
-    if output is not None:
-        output = list(output)
-        if len(output) != len(files):
-            raise ValueError(f"`output` has {len(output)} entries for {len(files)} files")
-        fmt_out = output_format.lower()
-        short = fmt_out.endswith("_m10")
-        base = fmt_out[:-4] if short else fmt_out
-        if base not in _WRITERS or (short and base not in _M10_FORMATS):  # (what `dumps` checks, and its message)
-            raise ValueError(f"Could not recognize alignment format: {output_format!r}")
-        emit = fmt_out if fmt_out in _lib.TEXT_FORMATS else None
+    output, emit = _check_output(output, output_format, len(files))
     if getattr(trimmer, "_platform", None) != "hip" or not (matrix is None or isinstance(matrix, SimilarityMatrix)):
         # (no device, or a matrix `trim` refuses: the composition itself, which raises what it raises where it raises it)
         # (`output` needs a device trim first: this raises before anything could be written)
         return trim_batch(trimmer, [Alignment.load(f, format) for f in files], matrix, device=device, threads=threads, shard=False,
                           masks_only=masks_only)
-    texts, failed = [], None  # (data, fmt) per file up to the first that cannot be read
+    texts, errors = _read_texts(files, format)
+    # FASTA texts: parsed and trimmed on the device (a record for every text that holds an alignment, parsed or not)
+    params3, _keep = trimmer._fasta_params(matrix)
+    on_device = [k for k, (data, fmt) in enumerate(texts) if fmt == "fasta" and 0 < len(data) <= _lib.FASTA_MAX_BYTES]
+    recs = {}
+    if on_device:
+        batch, outs = _on_native_batch(_device_index(device), threads, lambda b: b.trim_fasta(
+            [texts[k][0] for k in on_device], _VALID.view(np.uint8), params3, want_rows=not masks_only, emit=emit))
+        for k, rec in zip(on_device, outs):
+            if rec.parse_rc not in (_lib.OK, _lib.E_BAD_RESIDUE, _lib.E_LENGTH_MISMATCH):
+                batch.check(rec.parse_rc, rec.tinfo)  # a device failure (HIP, memory) is raised, never hidden behind the host path
+            if rec.info.m > 0 and rec.info.n > 0:
+                rec.batch, rec.data, rec.params = batch, texts[k][0], params3[type_index(rec.info.seq_type)]
+                recs[k] = rec
+    # the rest, and the texts without a record or with empty records, as Alignment.load reads them (its messages)
+    loaded = {}
+    for k, (data, fmt) in enumerate(texts):
+        if k not in recs:
+            try:
+                loaded[k] = Alignment._from_text(data if isinstance(data, bytes) else bytes(data), files[k], format, fmt)
+            except Exception as err:
+                errors[k] = err
+    for k in range(len(files)):  # the first file that does not load, in input order
+        if k in errors:
+            raise errors[k]
+        if k in recs and recs[k].parse_rc != _lib.OK:
+            raise _fasta_error(recs[k])
+    # ... through the row path (what trim_batch does with them)
+    prepared, outs, batch, _ = _trim_rows(trimmer, loaded.values(), matrix, device, threads)
+    for (k, a), (names, dense, _, params, _keep), out in zip(loaded.items(), prepared, outs):
+        res, seq, info, rc, rows = out or (None, None, None, _lib.OK, None)
+        recs[k] = _lib.TrimRecord(res, seq, info, rc, rows, dense, names=names, datatype=a._datatype, params=params, batch=batch)
+    for k in range(len(files)):  # trim failures, in input order
+        if recs[k].rc != _lib.OK:
+            recs[k].batch.check(recs[k].rc, recs[k].tinfo)
+    out = []
+    for k in range(len(files)):
+        rec = recs[k]
+        if rec.names is None and (not masks_only or rec.tinfo.warnings):  # (a device text's, out of the text: only when somebody reads them)
+            rec.names = _fasta_names(rec)
+        res, seq, t = _result(trimmer, rec.names, rec.rows, rec.datatype, rec.keep_res, rec.keep_seq, rec.tinfo, rec.only_gaps_rows,
+                              rec.params, masks_only)
+        if t is not None and rec.info is not None and res.all() and seq.all():
+            t._detected_type = rec.info.seq_type  # (nothing removed: the type the device detected is the result's)
+        out.append((np.asarray(res, dtype=bool), np.asarray(seq, dtype=bool)) if masks_only else t)
+    if output is not None:  # every file loaded, every trim succeeded: the outputs, in input order
+        for k, (data, fmt) in enumerate(texts):
+            _write_output(output[k], output_format, recs[k], out[k], lambda: Alignment._from_text(bytes(data), files[k], format, fmt))
+    return out
+
+
+def _check_output(output, output_format, count):
+    """`trim_files`'s `output` / `output_format` -> (the outputs as a list or None, the format for the device writer or None);
+    a `ValueError` for a wrong length and for a format `dumps` does not know (what it checks, and its message)."""
+    if output is None:
+        return None, None
+    output = list(output)
+    if len(output) != count:
+        raise ValueError(f"`output` has {len(output)} entries for {count} files")
+    fmt_out = output_format.lower()
+    short = fmt_out.endswith("_m10")
+    base = fmt_out[:-4] if short else fmt_out
+    if base not in _WRITERS or (short and base not in _M10_FORMATS):
+        raise ValueError(f"Could not recognize alignment format: {output_format!r}")
+    return output, (fmt_out if fmt_out in _lib.TEXT_FORMATS else None)
+
+
+def _read_texts(files, format):
+    """[(data: bytes or a mapping, format name)] for the files up to the first that cannot be read, and {its index: the error}"""
+    texts = []
     for k, f in enumerate(files):
         try:
             data = _read_input(f, format, mapped=True)
             fmt = format if format is not None else (_sniff_format(data) if isinstance(data, bytes) else _sniff_mapped(data))
             texts.append((data, fmt.lower()))
         except Exception as err:
-            failed = (k, err)
-            break
-    on_device = [k for k, (data, fmt) in enumerate(texts) if fmt == "fasta" and 0 < len(data) <= _lib.FASTA_MAX_BYTES]
-    params3, _keep = trimmer._fasta_params(matrix)
-    index = device.index if isinstance(device, torch.device) and device.index is not None else None
-    if index is None:
-        index = int(os.environ.get("PYTRIMAL_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-    workers = max(1, min(int(threads), 64))
-
-    def run(call):
-        for attempt in range(3):
-            batch = _native_batch(index, workers)
-            try:
-                return batch, call(batch)
-            except _lib.BatchClosed:  # (another thread replaced the device's batch object)
-                if attempt == 2:
-                    raise
-
-    done = {}
-    if on_device:
-        batch, outs = run(lambda b: b.trim_fasta([texts[k][0] for k in on_device], _VALID.view(np.uint8), params3,
-                                                  want_rows=not masks_only, emit=emit))
-        for k, rec in zip(on_device, outs):
-            if rec["parse_rc"] not in (_lib.OK, _lib.E_BAD_RESIDUE, _lib.E_LENGTH_MISMATCH):
-                batch.check(rec["parse_rc"], rec["tinfo"])  # a device failure (HIP, memory) is raised, never hidden behind the host path
-            if rec["info"].m > 0 and rec["info"].n > 0:
-                rec["batch"] = batch
-                done[k] = rec
-    # the rest, and the texts without a record or with empty records, as Alignment.load reads them (its messages)
-    loaded, errors = {}, {}
-    for k, (data, fmt) in enumerate(texts):
-        if k not in done:
-            try:
-                loaded[k] = Alignment._from_text(data if isinstance(data, bytes) else bytes(data), files[k], format, fmt)
-            except Exception as err:
-                errors[k] = err
-    if failed is not None:
-        errors[failed[0]] = failed[1]
-    for k in range(len(texts) + (failed is not None)):  # the first file that does not load, in input order
-        if k in errors:
-            raise errors[k]
-        if k in done and done[k]["parse_rc"] != _lib.OK:
-            raise _fasta_error(done[k], texts[k][0])
-    # the loaded ones through the row path (what trim_batch does with them)
-    prepared = {k: trimmer._prepare(a, matrix) for k, a in loaded.items()}
-    rows_todo = [k for k, p in prepared.items() if p[1].shape[0] and p[1].shape[1]]
-    if rows_todo:
-        batch, outs = run(lambda b: b.trim([(prepared[k][1], prepared[k][2], prepared[k][3]) for k in rows_todo]))
-        for k, o in zip(rows_todo, outs):
-            done[k] = {"rc": o[3], "tinfo": o[2], "batch": batch, "keep_res": o[0], "keep_seq": o[1], "only_gaps_rows": o[4]}
-    for k in sorted(done):  # trim failures, in input order
-        if done[k]["rc"] != _lib.OK:
-            done[k]["batch"].check(done[k]["rc"], done[k]["tinfo"])
-    out = []
-    for k, (data, _) in enumerate(texts):
-        rec = done.get(k)
-        if k in prepared:
-            names, dense, _, params, _ = prepared[k]
-            if rec is None:  # an empty alignment never reaches the device
-                rec = {"keep_res": np.ones(dense.shape[1], dtype=bool), "keep_seq": np.ones(dense.shape[0], dtype=bool), "tinfo": None,
-                       "only_gaps_rows": None}
-            datatype, ty = loaded[k]._datatype, None
-        else:
-            names, dense, ty = None, rec["rows"], rec["info"].seq_type
-            params, datatype = params3[0 if (ty & 4 or ty == 0) else (2 if ty & 8 else 1)], 0
-        tinfo = rec["tinfo"]
-        if masks_only:
-            if tinfo is not None and tinfo.warnings:
-                _raise_warnings(tinfo, names if names is not None else _fasta_names(rec, data), rec["only_gaps_rows"])
-            out.append((np.asarray(rec["keep_res"], dtype=bool), np.asarray(rec["keep_seq"], dtype=bool)))
-            continue
-        t = trimmer._finish(names if names is not None else _fasta_names(rec, data), dense, datatype, rec["keep_res"], rec["keep_seq"],
-                            tinfo, rec["only_gaps_rows"], None, params)
-        if ty is not None and rec["keep_res"].all() and rec["keep_seq"].all():
-            t._detected_type = ty  # (nothing removed: the type the device detected is the result's)
-        out.append(t)
-    if output is not None:  # every file loaded, every trim succeeded: the outputs, in input order
-        for k, (data, fmt) in enumerate(texts):
-            rec = done.get(k)
-            text = rec.get("text") if rec is not None else None
-            if text is None:  # the host writer, on the result object (or on what it would have been)
-                t = out[k]
-                if masks_only:
-                    res, seq = t
-                    if k in prepared:
-                        names, dense = prepared[k][0], prepared[k][1]
-                        t = TrimmedAlignment._from_parts(names, dense, loaded[k]._datatype, seq, res)
-                    else:  # parsed on the device and not composed there (a flag): its rows as the host reads them
-                        a = Alignment._from_text(data if isinstance(data, bytes) else bytes(data), files[k], format, fmt)
-                        t = TrimmedAlignment._from_parts(a._names, a._matrix, a._datatype, seq, res)
-                t.dump(output[k], output_format)
-            elif isinstance(output[k], (str, bytes, os.PathLike)):
-                with open(os.fspath(output[k]), "wb") as f:
-                    f.write(text)
-            else:
-                output[k].write(text)
-    return out
+            return texts, {k: err}
+    return texts, {}
 
 
-def _fasta_names(rec, data):
-    return [bytes(data[o:o + n]) for o, n in zip(rec["name_off"].tolist(), rec["name_len"].tolist())]
+def _write_output(target, output_format, rec, result, reload):
+    """One output of `trim_files`: the text the device composed, else the host writer on the result object -- or, with
+    `masks_only` (`result` is the mask pair), on what it would have been."""
+    if rec.text is None:
+        if isinstance(result, tuple):
+            res, seq = result
+            if rec.info is None:
+                result = TrimmedAlignment._from_parts(rec.names, rec.rows, rec.datatype, seq, res)
+            else:  # parsed on the device and not composed there (a flag): its rows as the host reads them
+                a = reload()
+                result = TrimmedAlignment._from_parts(a._names, a._matrix, a._datatype, seq, res)
+        result.dump(target, output_format)
+    else:
+        _write_bytes(target, rec.text)
 
 
-def _fasta_error(rec, data):
+def _fasta_names(rec):
+    return [bytes(rec.data[o:o + n]) for o, n in zip(rec.name_off.tolist(), rec.name_len.tolist())]
+
+
+def _fasta_error(rec):
     """The ValueError `Alignment.load` raises for this parse failure (alignment._load_native)."""
-    from . import _lib
-
-    d = rec["detail"]
-    if rec["parse_rc"] == _lib.E_LENGTH_MISMATCH:
-        return ValueError(f"Sequence length mismatch in sequence {d.row}: {d.col} != {rec['info'].n}")
-    name = _fasta_names(rec, data)[d.row]
+    d = rec.detail
+    if rec.parse_rc == _lib.E_LENGTH_MISMATCH:
+        return ValueError(f"Sequence length mismatch in sequence {d.row}: {d.col} != {rec.info.n}")
+    name = _fasta_names(rec)[d.row]
     return ValueError(f"The sequence \"{name.decode('ascii', 'replace')}\" has an unknown ({d.byte}) character")

@@ -4,6 +4,30 @@
 
 using namespace msai;
 
+// The arguments of ONE call of the batch object: msa_trim_batch (ROWS) or msa_trim_batch_fasta[_emit] (TEXTS).  The entry point
+// fills one of these completely, run_call copies it into the batch object for the call's duration and clears it at the end: no
+// member of one call kind survives into a call of the other.
+struct BatchCall {
+    enum Kind { NONE, ROWS, TEXTS } kind = NONE;
+    int32_t count = 0;
+    int32_t *rc = nullptr;
+    // ROWS
+    const uint8_t *const *data = nullptr;
+    const int32_t *m = nullptr, *n = nullptr;
+    const int64_t *ld = nullptr;
+    const uint8_t *indet = nullptr;
+    const msa_trim_params *params = nullptr;
+    uint8_t *const *keep_res = nullptr, *const *keep_seq = nullptr;
+    msa_trim_info *info = nullptr;
+    // TEXTS (what each of them gave: msa_batch::fasta)
+    const uint8_t *const *texts = nullptr;
+    const int64_t *lens = nullptr;
+    const uint8_t *valid = nullptr;
+    const msa_trim_params *params_by_type = nullptr;
+    bool want_rows = false;
+    int emit_format = -1;  // msa_trim_batch_fasta_emit: the MSA_TEXT_* format the workers compose behind the trim, -1 none
+};
+
 // ---- batches of independent alignments ----------------------------------------------------------------------------
 // The reference's batch idiom is a thread pool over `trimmer.trim` (README.md:136-152), possible because its `trim`
 // releases the interpreter lock for the whole computation (_trimal.pyx:1334-1359).  Here the pool is native: worker
@@ -12,6 +36,7 @@ using namespace msai;
 // alignment, the kernels of others and the host selection logic of yet others overlap on one GPU, with nothing of the
 // interpreter in between.
 struct msa_batch {
+    // -- the pool: lives as long as the object
     int device = 0;
     std::vector<msa_ctx *> ctxs;
     std::vector<std::thread> workers;
@@ -20,19 +45,7 @@ struct msa_batch {
     uint64_t generation = 0;
     bool stop = false;
     int running = 0;
-    // the call in flight
-    int32_t count = 0;
-    const uint8_t *const *data = nullptr;
-    const int32_t *m = nullptr, *n = nullptr;
-    const int64_t *ld = nullptr;
-    const uint8_t *indet = nullptr;
-    const msa_trim_params *params = nullptr;
-    uint8_t *const *keep_res = nullptr, *const *keep_seq = nullptr;
-    msa_trim_info *info = nullptr;
-    int32_t *rc = nullptr;
-    std::vector<int32_t> order;
-    std::atomic<int32_t> next{0};
-    std::vector<std::vector<int32_t>> only_gaps;  // per alignment: the rows behind MSA_W_ONLY_GAPS_SEQUENCES
+    bool in_call = false;
     struct Engine *engine = nullptr;              // the batched-kernel path (below), created on first use
     // the engine's host-side loops (packing rows for the upload, the selection step), shared with the workers that have
     // nothing else to do: engine_parallel_for
@@ -47,14 +60,12 @@ struct msa_batch {
     bool use_engine = true;                       // MSA_BATCH_ENGINE=0: every alignment through the workers (diagnostics, tests)
     double engine_max_work = 3e8;                 // m * m * n up to which the engine takes an alignment (MSA_BATCH_ENGINE_MAX)
     int engine_min_count = 40;                    // fewer eligible alignments than this go to the workers instead (MSA_BATCH_ENGINE_MIN)
-    bool in_call = false;
-    // a call of msa_trim_batch_fasta (texts != nullptr): the texts, and what each of them gave (kept until the next call)
-    const uint8_t *const *texts = nullptr;
-    const int64_t *lens = nullptr;
-    const uint8_t *valid = nullptr;
-    const msa_trim_params *params_by_type = nullptr;
-    bool want_rows = false;
-    int emit_format = -1;  // msa_trim_batch_fasta_emit: the MSA_TEXT_* format the workers compose behind the trim, -1 none
+    // -- the call in flight (run_call), and the workers' share of it, largest first
+    BatchCall call;
+    std::vector<int32_t> order;
+    std::atomic<int32_t> next{0};
+    // -- what a call leaves behind, valid until the next call of either kind
+    std::vector<std::vector<int32_t>> only_gaps;  // per alignment: the rows behind MSA_W_ONLY_GAPS_SEQUENCES
     struct FastaResult {
         int parse_rc = MSA_OK;
         msa_text_info info{};
@@ -67,7 +78,7 @@ struct msa_batch {
         int64_t text_len = -1;            // -1: none
         uint32_t text_flags = 0;          // MSA_TEXT_F_*
     };
-    std::vector<FastaResult> fasta;
+    std::vector<FastaResult> fasta;  // per text of the last TEXTS call (none after a ROWS call)
 };
 
 // ---- the batch engine: one launch per kernel family for a whole group of alignments -------------------------------------
@@ -85,9 +96,10 @@ struct msa_batch {
 struct Engine {
     struct Item {
         int32_t k;            // index in the call
+        EngineKind kind;      // what its trim needs of the device: decided once per call (engine_takes)
         size_t res_word;      // offset (words) of its block in the result region: flags[16] gaps[npad] indets[npad] rowtot[mpad] mdk[n] q[n]
         int npad, mpad;
-        size_t extra_word;    // ... and of what its kind adds behind them (engine_needs 3 - 5)
+        size_t extra_word;    // ... and of what its kind adds behind them (ENGINE_OVERLAP, _REPRESENTATIVE, _DIGESTS)
     };
     struct Lane {
         // two queues per group: uploads and the short VALU-bound kernels (counts, planes, pair pass, lists) at HIGH priority,
@@ -100,7 +112,6 @@ struct Engine {
         PinBuf<uint8_t> h_meta, h_res, h_stage;
         uint64_t sig = 0;
         std::vector<Item> items;
-        size_t res_words = 0;
         bool busy = false;
     };
     static constexpr int MAX_LANES = 4;
@@ -117,53 +128,54 @@ namespace msai {
 
 inline size_t align_up(size_t x, size_t q) { return (x + q - 1) / q * q; }
 
-// Can the engine take alignment k?  (the similarity pipeline's conditions, one pair-pass regime, 32-bit list offsets, rows the
-// copy engine takes in one piece or that are small enough to pack on the way)
-// what a trim needs of the device: 0 not a trim the engine knows, 1 the gap statistics alone (gappyout, nogaps, noallgaps, a
-// manual gap threshold), 2 the similarity pipeline as well, 3 - 5 the trimmers that remove sequences (below)
-int engine_needs(const msa_trim_params *p) {
+// what a trim needs of the device (EngineKind, msastat_ctx.h)
+EngineKind engine_needs(const msa_trim_params *p) {
     const int method = p->method;
     // the trimmers that remove sequences (round 6): their statistics come back with the group's one copy as well, and the
-    // selection runs on the host-only view -- 3 OverlapTrimmer (the overlap counts of every sequence), 4 RepresentativeTrimmer
-    // (the identities: clustered on the host, threshold mode and clusters=K alike), 5 noduplicateseqs (row digests)
-    if (method == MSA_METHOD_NODUPLICATESEQS) return 5;
-    if (p->clusters != -1 || p->max_identity != -1) return 4;
-    if (p->residue_overlap != -1 && p->sequence_overlap != -1) return 3;
+    // selection runs on the host-only view -- OverlapTrimmer (the overlap counts of every sequence), RepresentativeTrimmer
+    // (the identities: clustered on the host, threshold mode and clusters=K alike), noduplicateseqs (row digests)
+    if (method == MSA_METHOD_NODUPLICATESEQS) return ENGINE_DIGESTS;
+    if (p->clusters != -1 || p->max_identity != -1) return ENGINE_REPRESENTATIVE;
+    if (p->residue_overlap != -1 && p->sequence_overlap != -1) return ENGINE_OVERLAP;
     if (method == MSA_METHOD_STRICT || method == MSA_METHOD_STRICTPLUS || method == MSA_METHOD_AUTOMATED1 ||
         (method == MSA_METHOD_NONE && p->similarity_threshold != -1))
-        return 2;
+        return ENGINE_SIMILARITY;
     if (method == MSA_METHOD_GAPPYOUT || method == MSA_METHOD_NOGAPS || method == MSA_METHOD_NOALLGAPS ||
         (method == MSA_METHOD_NONE && (p->gap_threshold != -1 || p->gap_absolute_threshold != -1)))
-        return 1;
-    return 0;
+        return ENGINE_GAPS;
+    return ENGINE_NONE;
 }
 
-bool engine_takes(const msa_batch *b, int32_t k, const msa_trim_params *ref) {
-    const msa_trim_params *p = b->params + k;
-    const int m = b->m[k], n = b->n[k];
-    if (m < 2 || n < 1 || m > 32768 || !b->data[k] || b->ld[k] < n) return false;
-    const int needs = engine_needs(p);
-    if (!needs) return false;
+// Does the engine take alignment k, and as what?  ENGINE_NONE: no.  (the similarity pipeline's conditions, one pair-pass regime,
+// 32-bit list offsets, rows the copy engine takes in one piece or that are small enough to pack on the way)
+EngineKind engine_takes(const msa_batch *b, int32_t k, const msa_trim_params *ref) {
+    const BatchCall &c = b->call;
+    const msa_trim_params *p = c.params + k;
+    const int m = c.m[k], n = c.n[k];
+    if (m < 2 || n < 1 || m > 32768 || !c.data[k] || c.ld[k] < n) return ENGINE_NONE;
+    const EngineKind needs = engine_needs(p);
+    if (needs == ENGINE_NONE) return ENGINE_NONE;
     int gap_hw = p->gap_window, sim_hw = p->similarity_window;
     if (p->window != -1) gap_hw = sim_hw = p->window;
     // (a gap window is host work on the counts -- unless the similarity pipeline follows: its ">= 80 % gaps" cut reads the windowed
     // counts on the device)
-    if (gap_hw > 0 && needs == 2) return false;
-    if (gap_hw > n / 4) return false;  // (an error return: the ordinary path reports it)
-    if (needs == 1 || needs == 3 || needs == 5) return (double)m * n <= 4e6;  // (one pass over the rows: small alignments, where launches are the cost)
-    if (needs == 4) {  // the pair pass, and m x m identities in the group's copy back
+    if (gap_hw > 0 && needs == ENGINE_SIMILARITY) return ENGINE_NONE;
+    if (gap_hw > n / 4) return ENGINE_NONE;  // (an error return: the ordinary path reports it)
+    if (needs == ENGINE_GAPS || needs == ENGINE_OVERLAP || needs == ENGINE_DIGESTS)
+        return (double)m * n <= 4e6 ? needs : ENGINE_NONE;  // (one pass over the rows: small alignments, where launches are the cost)
+    if (needs == ENGINE_REPRESENTATIVE) {  // the pair pass, and m x m identities in the group's copy back
         const int m_pad4 = round_up(m, 128);
-        return m <= 1024 && msak::pair_pipe_regime(m, m_pad4) && (double)m * m * n <= b->engine_max_work;
+        return m <= 1024 && msak::pair_pipe_regime(m, m_pad4) && (double)m * m * n <= b->engine_max_work ? needs : ENGINE_NONE;
     }
-    if (sim_hw > n / 4) return false;
-    if (!p->vhash || !p->dist || p->npos < 1 || p->npos > 28) return false;
+    if (sim_hw > n / 4) return ENGINE_NONE;
+    if (!p->vhash || !p->dist || p->npos < 1 || p->npos > 28) return ENGINE_NONE;
     // one set of tables per call: the first taken alignment's
-    if (ref && (ref->npos != p->npos || b->indet[k] != b->indet[ref - b->params] ||
+    if (ref && (ref->npos != p->npos || c.indet[k] != c.indet[ref - c.params] ||
                 (ref->vhash != p->vhash && std::memcmp(ref->vhash, p->vhash, 26 * sizeof(int32_t)) != 0) ||
                 (ref->dist != p->dist && std::memcmp(ref->dist, p->dist, sizeof(float) * p->npos * p->npos) != 0)))
-        return false;
+        return ENGINE_NONE;
     const int m_pad = round_up(m, 128);
-    if (!msak::pair_pipe_regime(m, m_pad)) return false;
+    if (!msak::pair_pipe_regime(m, m_pad)) return ENGINE_NONE;
     // Where the batched kernels pay: alignments that do not fill the chip by themselves.  From ~600 x 2500 on a context per
     // alignment (four workers) is as fast or faster -- the similarity kernel bounds both (64 x 1000 x 4000: 23.8 ms of it in
     // either scheme), and four alignments in flight overlap the VALU-bound pair pass of one with the similarity kernel of
@@ -171,182 +183,208 @@ bool engine_takes(const msa_batch *b, int32_t k, const msa_trim_params *ref) {
     // 10.2 against 30 through trim_batch).  Since a worker's trim of a small alignment is the compact pipeline the line lies lower:
     // 128 x 500 x 2000 12.8 against 11.7 for the workers, 256 x 300 x 1200 11.0 against 15.2 for the engine.
     // MSA_BATCH_ENGINE_MAX: the m * m * n up to which the engine takes an alignment.
-    if ((double)m * m * n > b->engine_max_work) return false;
-    if ((double)m * m * 12 + (double)msak::bx_cols_pad(n) * msak::bx_ldk(m) * 7 > 6e9) return false;  // (a few GB per alignment: one at a time)
-    return true;
+    if ((double)m * m * n > b->engine_max_work) return ENGINE_NONE;
+    if ((double)m * m * 12 + (double)msak::bx_cols_pad(n) * msak::bx_ldk(m) * 7 > 6e9) return ENGINE_NONE;  // (a few GB per alignment: one at a time)
+    return needs;
 }
 
 int engine_parallel_for(msa_batch *b, int32_t total, std::function<void(int32_t, int)> fn);
 
-struct EngineLayout {  // byte offsets of one alignment's arrays in the arena
-    size_t raw, planes, ident, w, wlow, wbar, row_avg, row_max, codeT, codeR, off, trow, nvalid, simnum, simden, simstate, cols, end;
+// fn() with its exceptions as return codes: none may leave a worker thread (std::terminate would take the caller's process
+// with it) or the C ABI
+template <class F>
+static int no_throw(F fn) {
+    try {
+        return fn();
+    } catch (const std::bad_alloc &) {
+        return MSA_E_NOMEM;
+    } catch (...) {
+        return MSA_E_INVALID;
+    }
+}
+
+// one alignment of a ROWS call on context ctx (a worker's, or the engine's own for a second pass): upload without waiting, trim
+static int rows_item(msa_batch *b, msa_ctx *ctx, int32_t k) {
+    const BatchCall &c = b->call;
+    msa_trim_info local;
+    msa_trim_info *info = c.info ? c.info + k : &local;
+    ctx->only_gaps_rows.clear();
+    int rc = msa_upload_packed_async(ctx, c.data[k], c.m[k], c.n[k], c.ld[k], c.indet[k]);
+    if (rc == MSA_OK) {
+        rc = msa_trim(ctx, c.params + k, c.keep_res[k], c.keep_seq[k], info);
+    } else {
+        std::memset(info, 0, sizeof(*info));
+        (void)hipStreamSynchronize(ctx->stream);  // (nothing of a failed upload may stay in flight over the caller's rows)
+    }
+    b->only_gaps[k] = ctx->only_gaps_rows;
+    return rc;
+}
+
+struct EngineLayout {  // byte offsets of one alignment's arrays in the arena (0: its kind has no such array)
+    size_t raw, planes, ident, w, wlow, wbar, row_avg, row_max, codeT, codeR, off, trow, nvalid, simnum, simden, simstate, cols;
 };
 
-int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<int32_t> &ks) {
-    msa_ctx *tc = e->tables;
-    const int K = (int)ks.size();
-    if (!L.stream) {
-        int least = 0, greatest = 0;
-        HIPCHK(tc, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(tc, hipStreamCreateWithPriority(&L.pre, hipStreamNonBlocking, greatest));
-        HIPCHK(tc, hipStreamCreateWithPriority(&L.stream, hipStreamNonBlocking, least));
-        HIPCHK(tc, hipEventCreateWithFlags(&L.prepared, hipEventDisableTiming));
-        HIPCHK(tc, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
-    }
-    // layout: the result region first (one memset, one copy), then the alignments' arrays
-    std::vector<EngineLayout> lay(K);
-    L.items.resize(K);
-    size_t res_words = 0, stage_bytes = 0;
+// What engine_layout decides for one group: where everything lies in the arena, which kernels run, the signature of both.
+struct EngineGroup {
+    std::vector<EngineLayout> lay;
+    size_t res_words = 0, raw_base = 0, raw_bytes = 0, arena_bytes = 0;
     int max_m = 0, any_sim = -1;  // (over the alignments that run the similarity pipeline)
+    bool multi = false, cols_mode = false, sort_cols = false;
     uint64_t sig = 1469598103934665603ull;
-    auto mix = [&](uint64_t v) { sig = (sig ^ v) * 1099511628211ull; };
+    void mix(uint64_t v) { sig = (sig ^ v) * 1099511628211ull; }
+    // how each alignment's rows reach the arena (engine_row_routes): packed into the staging buffer, fetched by a kernel
+    // (page-locked rows as the device sees them: read by fetch_rows_batch_kernel), or neither -- a copy of its own
+    std::vector<uint8_t> packed;
+    std::vector<const uint8_t *> fetch;
+    bool any_packed = false;
+};
+
+// the kernel families of a group: one prefix-sum array of blocks each (F_ENCODE / F_COLS: by mode)
+enum { F_FETCH, F_GAPS, F_ROWTOT, F_PLANES, F_PAIRS, F_WMEANS, F_IDROWS, F_ENCODE, F_COMPACT, F_FINISH, F_COLS, F_OVERLAP, F_DIGEST, F_COUNT };
+
+// the metadata block of a group of K: [BAlign K][LgAlign K][prefix arrays: F_COUNT x (K + 1)], on the host and on the device
+struct EngineMeta {
+    msak::BAlign *bt;
+    msak::LgAlign *lt;
+    int32_t *pf;
+};
+static size_t engine_meta_bytes(int K) {
+    return align_up((size_t)K * sizeof(msak::BAlign), 256) + align_up((size_t)K * sizeof(msak::LgAlign), 256) +
+           align_up((size_t)F_COUNT * (K + 1) * sizeof(int32_t), 256);
+}
+static EngineMeta engine_meta(uint8_t *base, int K) {
+    uint8_t *lt = base + align_up((size_t)K * sizeof(msak::BAlign), 256);
+    return {reinterpret_cast<msak::BAlign *>(base), reinterpret_cast<msak::LgAlign *>(lt),
+            reinterpret_cast<int32_t *>(lt + align_up((size_t)K * sizeof(msak::LgAlign), 256))};
+}
+
+// The arena layout of a group: the result region first (one memset, one copy), then the rows of every alignment side by side,
+// then the derived arrays.  Fills the items' places in the result region.
+static EngineGroup engine_layout(const BatchCall &c, const Engine *e, std::vector<Engine::Item> &items) {
+    const int K = (int)items.size();
+    EngineGroup g;
+    g.lay.assign(K, EngineLayout{});
     for (int i = 0; i < K; ++i) {
-        const int k = ks[i], m = b->m[k], n = b->n[k];
-        Engine::Item &it = L.items[i];
-        it.k = k;
+        Engine::Item &it = items[i];
+        const int m = c.m[it.k], n = c.n[it.k];
         it.npad = round_up(n + 64, 64);
         it.mpad = round_up(m + 64, 64);
-        it.res_word = res_words;
-        res_words += 16 + (size_t)2 * it.npad + it.mpad + (size_t)2 * it.npad;
-        const int kind = engine_needs(b->params + k);
-        if (kind == 2) max_m = std::max(max_m, m), any_sim = i;
+        it.res_word = g.res_words;
+        g.res_words += 16 + (size_t)2 * it.npad + it.mpad + (size_t)2 * it.npad;
+        if (it.kind == ENGINE_SIMILARITY) g.max_m = std::max(g.max_m, m), g.any_sim = i;
         // what the kind brings back beside the common vectors: overlap counts [mpad]; identities [m][ldw]; lengths [mpad] + hashes
-        it.extra_word = res_words;
-        res_words += kind == 3 ? (size_t)it.mpad : kind == 4 ? (size_t)m * round_up(m, 64) : kind == 5 ? (size_t)5 * it.mpad : 0;
-        mix(((uint64_t)(uint32_t)m << 32) | (uint32_t)n);
-        mix(b->params[k].method == MSA_METHOD_AUTOMATED1);
-        mix(engine_needs(b->params + k));
+        it.extra_word = g.res_words;
+        g.res_words += it.kind == ENGINE_OVERLAP          ? (size_t)it.mpad
+                       : it.kind == ENGINE_REPRESENTATIVE ? (size_t)m * round_up(m, 64)
+                       : it.kind == ENGINE_DIGESTS        ? (size_t)5 * it.mpad
+                                                          : 0;
+        g.mix(((uint64_t)(uint32_t)m << 32) | (uint32_t)n);
+        g.mix(c.params[it.k].method == MSA_METHOD_AUTOMATED1);
+        g.mix(it.kind);
     }
-    const bool multi = msak::lg_rounds_per_launch(max_m) > 0;  // (the similarity kernel in several launches: per-column state)
+    g.multi = msak::lg_rounds_per_launch(g.max_m) > 0;  // (the similarity kernel in several launches: per-column state)
     // groups of small alignments: the similarity statistic with a lane per column (similarity_cols_batch_kernel) -- no
     // column-major codes, no lists
-    const bool cols_mode = max_m <= e->cols_max_m;
-    mix(cols_mode);
+    g.cols_mode = g.max_m <= e->cols_max_m;
+    g.mix(g.cols_mode);
     // the wave-per-column kernel's columns dealt by weight, alignment by alignment (a counting sort per alignment on the device,
     // behind the gap counts: workgroups of four columns of like weight, the heaviest first -- over the columns as they lie a
     // workgroup's slots are held until its heaviest column is done: profiles/r05_engine_sort_ab.txt)
-    const bool sort_cols = !cols_mode && any_sim >= 0 && max_m <= 15000;  // (the sort's bins live in LDS)
-    mix(sort_cols);
-    size_t off = align_up(res_words * 4, 4096);
+    g.sort_cols = !g.cols_mode && g.any_sim >= 0 && g.max_m <= 15000;  // (the sort's bins live in LDS)
+    g.mix(g.sort_cols);
+    size_t off = align_up(g.res_words * 4, 4096);
     auto take = [&](size_t bytes) {
         const size_t at = off;
         off = align_up(off + bytes, 256);
         return at;
     };
-    // the rows of every alignment side by side, then the derived arrays.  Rows the copy engine takes as they lie (page-locked,
-    // or 16-byte aligned rows of a multiple of 16 bytes) go up in a copy each -- 8 us of the copy queue per small alignment,
-    // beside the kernels of the group before; the others are packed into pinned staging at the same offsets (the calling
-    // thread and the idle workers) and go up in one copy per run.  (Packing everything small, measured: 1.7 ms of five
-    // threads per 25 MB of cache-cold rows against 2.1 ms of copy queue that nobody waits for.)
-    const size_t raw_base = off;
-    std::vector<uint8_t> packed(K, 0);
-    std::vector<const uint8_t *> fetch(K, nullptr);  // page-locked rows as the device sees them: read by fetch_rows_batch_kernel
+    g.raw_base = off;
+    for (int i = 0; i < K; ++i) g.lay[i].raw = take((size_t)c.m[items[i].k] * round_up(c.n[items[i].k], 64) + 256);
+    g.raw_bytes = off - g.raw_base;
     for (int i = 0; i < K; ++i) {
-        const int k = ks[i], m = b->m[k], n = b->n[k];
-        const size_t ld = round_up(n, 64);
-        lay[i].raw = take((size_t)m * ld + 256);
-        const uint8_t *rows = b->data[k];
-        const int64_t hld = b->ld[k];
+        const int m = c.m[items[i].k], n = c.n[items[i].k];
+        const size_t ld = round_up(n, 64), nchunk = (n + 31) / 32, m_pad = round_up(m, 128), ldw = round_up(m, 64);
+        const size_t ncp = msak::bx_cols_pad(n), ldk = msak::bx_ldk(m);
+        EngineLayout &y = g.lay[i];
+        const EngineKind kind = items[i].kind;
+        // RepresentativeTrimmer: planes and the pair pass; the identities land in the result region.  The gap statistics (and what
+        // one more pass over the rows computes): the rows are all it needs on the device
+        if (kind == ENGINE_REPRESENTATIVE || kind == ENGINE_SIMILARITY) y.planes = take(((size_t)msak::planes_total() * nchunk * m_pad + 64) * 4);
+        if (kind == ENGINE_SIMILARITY) {
+            y.ident = take(((size_t)m * ldw + 512) * 4);
+            y.w = take(((size_t)m * ldw + 512) * 4);
+            y.wlow = take((msak::bx_wlow_rows(m) + 2) * ldw * 4);
+            y.wbar = take(((size_t)m + 128) * 4);
+            y.row_avg = take(((size_t)m + 64) * 4);
+            y.row_max = take(((size_t)m + 64) * 4);
+            if (g.cols_mode) {
+                y.codeR = take((size_t)m * ld + 256);
+            } else {
+                y.codeT = take(ncp * ldk + 64);
+                y.off = take((ncp * ldk + 64) * 4);
+                y.trow = take((ncp * ldk + 64) * 2);
+                y.nvalid = take((ncp + 64) * 4);
+            }
+            y.simnum = take(((size_t)n + 64) * 4);
+            y.simden = take(((size_t)n + 64) * 4);
+            y.simstate = g.multi ? take(msak::lg_state_floats(n) * 4) : 0;
+            y.cols = g.sort_cols ? take(((size_t)n + 64) * 4) : 0;  // (the wave-per-column kernel's columns by weight: sort_columns_batch)
+        }
+    }
+    g.mix(g.multi);
+    g.arena_bytes = off;
+    return g;
+}
+
+// How the rows of every alignment of the group go up.  Rows the copy engine takes as they lie (page-locked, or 16-byte aligned
+// rows of a multiple of 16 bytes) go up in a copy each -- 8 us of the copy queue per small alignment, beside the kernels of the
+// group before; the others are packed into pinned staging at the same offsets (the calling thread and the idle workers) and go
+// up in one copy per run.  (Packing everything small, measured: 1.7 ms of five threads per 25 MB of cache-cold rows against
+// 2.1 ms of copy queue that nobody waits for.)
+static void engine_row_routes(const BatchCall &c, const Engine *e, const std::vector<Engine::Item> &items, EngineGroup &g) {
+    const int K = (int)items.size();
+    g.packed.assign(K, 0);
+    g.fetch.assign(K, nullptr);
+    for (int i = 0; i < K; ++i) {
+        const int k = items[i].k, m = c.m[k];
+        const size_t ld = round_up(c.n[k], 64);
+        const uint8_t *rows = c.data[k];
+        const int64_t hld = c.ld[k];
         bool locked = false;
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, rows) == hipSuccess) locked = at.type == hipMemoryTypeHost;
         else (void)hipGetLastError();
         const bool direct = hld == (int64_t)ld || (locked && hld % 8 == 0) || (hld % 16 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0);
-        packed[i] = !direct;
+        g.packed[i] = !direct;
         // small page-locked alignments: the device fetches the rows itself (one launch per group); big ones keep their copy
         // (one DMA transfer at the link's rate needs no help)
         if (locked && e->fetch_max_bytes > 0 && (size_t)m * ld <= (size_t)e->fetch_max_bytes) {
             void *dp = nullptr;
             if (hipHostGetDevicePointer(&dp, const_cast<uint8_t *>(rows), 0) == hipSuccess && dp) {
-                fetch[i] = static_cast<const uint8_t *>(dp);
-                packed[i] = 0;
+                g.fetch[i] = static_cast<const uint8_t *>(dp);
+                g.packed[i] = 0;
             } else {
                 (void)hipGetLastError();
             }
         }
     }
-    const size_t raw_bytes = off - raw_base;
-    for (int i = 0; i < K; ++i) {
-        const int k = ks[i], m = b->m[k], n = b->n[k];
-        const size_t ld = round_up(n, 64), nchunk = (n + 31) / 32, m_pad = round_up(m, 128), ldw = round_up(m, 64);
-        const size_t ncp = msak::bx_cols_pad(n), ldk = msak::bx_ldk(m);
-        EngineLayout &y = lay[i];
-        const int kind = engine_needs(b->params + k);
-        if (kind == 4) {  // RepresentativeTrimmer: planes and the pair pass; the identities land in the result region
-            y.ident = y.w = y.wlow = y.wbar = y.row_avg = y.row_max = y.codeT = y.codeR = y.off = y.trow = y.nvalid = y.simnum = y.simden =
-                y.simstate = y.cols = 0;
-            y.planes = take(((size_t)msak::planes_total() * nchunk * m_pad + 64) * 4);
-            y.end = off;
-            continue;
-        }
-        if (kind != 2) {  // the gap statistics (and what one more pass over the rows computes): the rows are all it needs on the device
-            y.planes = y.ident = y.w = y.wlow = y.wbar = y.row_avg = y.row_max = y.codeT = y.codeR = y.off = y.trow = y.nvalid = y.simnum =
-                y.simden = y.simstate = 0;
-            y.end = off;
-            continue;
-        }
-        y.planes = take(((size_t)msak::planes_total() * nchunk * m_pad + 64) * 4);
-        y.ident = take(((size_t)m * ldw + 512) * 4);
-        y.w = take(((size_t)m * ldw + 512) * 4);
-        y.wlow = take((msak::bx_wlow_rows(m) + 2) * ldw * 4);
-        y.wbar = take(((size_t)m + 128) * 4);
-        y.row_avg = take(((size_t)m + 64) * 4);
-        y.row_max = take(((size_t)m + 64) * 4);
-        y.codeT = y.codeR = y.off = y.trow = y.nvalid = 0;
-        if (cols_mode) {
-            y.codeR = take((size_t)m * ld + 256);
-        } else {
-            y.codeT = take(ncp * ldk + 64);
-            y.off = take((ncp * ldk + 64) * 4);
-            y.trow = take((ncp * ldk + 64) * 2);
-            y.nvalid = take((ncp + 64) * 4);
-        }
-        y.simnum = take(((size_t)n + 64) * 4);
-        y.simden = take(((size_t)n + 64) * 4);
-        y.simstate = multi ? take(msak::lg_state_floats(n) * 4) : 0;
-        y.cols = sort_cols ? take(((size_t)n + 64) * 4) : 0;  // (the wave-per-column kernel's columns by weight: sort_columns_batch)
-        y.end = off;
-    }
-    if (std::find(packed.begin(), packed.end(), 1) != packed.end()) stage_bytes = raw_bytes;  // (the staging mirrors the raw region)
-    mix(multi);
-    const size_t arena_bytes = off;
-    const uint8_t *old_base = L.arena.p;
-    HIPCHK(tc, L.arena.reserve(arena_bytes));
-    mix((uint64_t)(uintptr_t)L.arena.p);
-    // tables: [BAlign K][LgAlign K][prefix arrays: F x (K + 1)]
-    enum { F_FETCH, F_GAPS, F_ROWTOT, F_PLANES, F_PAIRS, F_WMEANS, F_IDROWS, F_ENCODE, F_COMPACT, F_FINISH, F_COLS, F_OVERLAP, F_DIGEST, F_COUNT };  // (F_ENCODE / F_COLS: by mode)
-    const size_t meta_bytes = align_up((size_t)K * sizeof(msak::BAlign), 256) + align_up((size_t)K * sizeof(msak::LgAlign), 256) +
-                              align_up((size_t)F_COUNT * (K + 1) * sizeof(int32_t), 256);
-    HIPCHK(tc, L.meta.reserve(meta_bytes));
-    HIPCHK(tc, L.h_meta.reserve(meta_bytes));
-    HIPCHK(tc, L.h_res.reserve(res_words * 4 + 64));
-    if (stage_bytes) {
-        // (a grown staging buffer starts as zeros: the runs copied out of it span the slack and the alignment gaps between the packed
-        // alignments, which only ever hold what the buffer held when it was allocated -- the arena's padding stays zero whatever
-        // way the rows arrive)
-        const size_t had = L.h_stage.cap;
-        HIPCHK(tc, L.h_stage.reserve(stage_bytes));
-        if (L.h_stage.cap != had) std::memset(L.h_stage.p, 0, L.h_stage.cap);
-    }
-    (void)old_base;
+    g.any_packed = std::find(g.packed.begin(), g.packed.end(), 1) != g.packed.end();
+}
+
+// The descriptor tables of a group and the block prefix sums of its kernel families, into the host copy `h` of the metadata.
+static void engine_tables(const BatchCall &c, const Engine::Lane &L, const EngineGroup &g, const EngineMeta &h) {
+    const int K = (int)L.items.size();
     uint8_t *A = L.arena.p;
-    msak::BAlign *bt = reinterpret_cast<msak::BAlign *>(L.h_meta.p);
-    msak::LgAlign *lt = reinterpret_cast<msak::LgAlign *>(L.h_meta.p + align_up((size_t)K * sizeof(msak::BAlign), 256));
-    int32_t *pf = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(lt) + align_up((size_t)K * sizeof(msak::LgAlign), 256));
-    uint8_t *meta_d = L.meta.p;
-    const msak::BAlign *bt_d = reinterpret_cast<const msak::BAlign *>(meta_d);
-    const msak::LgAlign *lt_d = reinterpret_cast<const msak::LgAlign *>(meta_d + align_up((size_t)K * sizeof(msak::BAlign), 256));
-    const int32_t *pf_d = reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(lt_d) + align_up((size_t)K * sizeof(msak::LgAlign), 256));
-    for (int f = 0; f < F_COUNT; ++f) pf[(size_t)f * (K + 1)] = 0;
     int32_t *res_d = reinterpret_cast<int32_t *>(A);
+    for (int f = 0; f < F_COUNT; ++f) h.pf[(size_t)f * (K + 1)] = 0;
     for (int i = 0; i < K; ++i) {
-        const int k = ks[i], m = b->m[k], n = b->n[k];
         const Engine::Item &it = L.items[i];
-        const EngineLayout &y = lay[i];
+        const int k = it.k, m = c.m[k], n = c.n[k];
+        const EngineLayout &y = g.lay[i];
         msak::BAlign d = {};
         d.raw = A + y.raw;
-        d.fetch_src = fetch[i];
-        d.fetch_ld = b->ld[k];
+        d.fetch_src = g.fetch[i];
+        d.fetch_ld = c.ld[k];
         d.ld = round_up(n, 64);
         d.ldk = msak::bx_ldk(m);
         d.planes = reinterpret_cast<uint32_t *>(A + y.planes);
@@ -355,14 +393,14 @@ int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<i
         d.indets = d.gaps + it.npad;
         d.rowtot = d.indets + it.npad;
         d.mdk = reinterpret_cast<float *>(d.rowtot + it.mpad);
-        d.kind = engine_needs(b->params + k);
+        d.kind = it.kind;
         d.extra = res_d + it.extra_word;
-        d.gated = d.kind == 2 && b->params[k].method == MSA_METHOD_AUTOMATED1;
+        d.gated = it.kind == ENGINE_SIMILARITY && c.params[k].method == MSA_METHOD_AUTOMATED1;
         d.ident = d.gated ? reinterpret_cast<float *>(A + y.ident) : nullptr;
         d.w = reinterpret_cast<float *>(A + y.w);
         d.wlow = reinterpret_cast<float *>(A + y.wlow);
-        if (d.kind == 4) d.ident = reinterpret_cast<float *>(d.extra), d.w = nullptr, d.wlow = nullptr;
-        if (d.kind == 3) d.ov_need = static_cast<int>(std::ceil(b->params[k].residue_overlap * static_cast<float>(m - 1)));
+        if (it.kind == ENGINE_REPRESENTATIVE) d.ident = reinterpret_cast<float *>(d.extra), d.w = nullptr, d.wlow = nullptr;
+        if (it.kind == ENGINE_OVERLAP) d.ov_need = static_cast<int>(std::ceil(c.params[k].residue_overlap * static_cast<float>(m - 1)));
         d.wbar = reinterpret_cast<float *>(A + y.wbar);
         d.row_avg = reinterpret_cast<float *>(A + y.row_avg);
         d.row_max = reinterpret_cast<float *>(A + y.row_max);
@@ -375,59 +413,55 @@ int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<i
         d.simden = reinterpret_cast<float *>(A + y.simden);
         d.m = m, d.n = n, d.nchunk = (n + 31) / 32, d.m_pad = round_up(m, 128), d.ldw = round_up(m, 64);
         d.ncols_pad = msak::bx_cols_pad(n);
-        d.indet4 = 0x01010101u * b->indet[k];
-        bt[i] = d;
-        msak::LgAlign g = {};
-        g.voff = d.off, g.vtrow = d.trow, g.nvalid = d.nvalid, g.codeT = d.codeT;
-        g.wlow = d.wlow, g.wup = d.w, g.wbar = d.wbar, g.num_out = d.simnum, g.den_out = d.simden;
-        g.state = multi ? reinterpret_cast<float *>(A + y.simstate) : nullptr;
-        g.gate = d.gated ? d.flags + ST_GATE : nullptr;
-        const bool sim = d.kind == 2;
+        d.indet4 = 0x01010101u * c.indet[k];
+        h.bt[i] = d;
+        msak::LgAlign l = {};
+        l.voff = d.off, l.vtrow = d.trow, l.nvalid = d.nvalid, l.codeT = d.codeT;
+        l.wlow = d.wlow, l.wup = d.w, l.wbar = d.wbar, l.num_out = d.simnum, l.den_out = d.simden;
+        l.state = g.multi ? reinterpret_cast<float *>(A + y.simstate) : nullptr;
+        l.gate = d.gated ? d.flags + ST_GATE : nullptr;
+        const bool sim = it.kind == ENGINE_SIMILARITY;
         // (only the alignments whose trim runs the similarity kernel: max_m -- the sort's LDS bins -- is taken over those)
-        g.cols = sort_cols && sim ? reinterpret_cast<const int32_t *>(A + y.cols) : nullptr;
-        g.ldk = d.ldk, g.m = m, g.n = n, g.ldw = d.ldw, g.ncols = n;
-        lt[i] = g;
+        l.cols = g.sort_cols && sim ? reinterpret_cast<const int32_t *>(A + y.cols) : nullptr;
+        l.ldk = d.ldk, l.m = m, l.n = n, l.ldw = d.ldw, l.ncols = n;
+        h.lt[i] = l;
         auto add = [&](int f, int blocks) {
-            const bool runs = sim || f <= F_ROWTOT || (d.kind == 4 && (f == F_PLANES || f == F_PAIRS)) || (d.kind == 3 && f == F_OVERLAP) ||
-                              (d.kind == 5 && f == F_DIGEST);
-            pf[(size_t)f * (K + 1) + i + 1] = pf[(size_t)f * (K + 1) + i] + (runs ? blocks : 0);
+            const bool runs = sim || f <= F_ROWTOT || (it.kind == ENGINE_REPRESENTATIVE && (f == F_PLANES || f == F_PAIRS)) ||
+                              (it.kind == ENGINE_OVERLAP && f == F_OVERLAP) || (it.kind == ENGINE_DIGESTS && f == F_DIGEST);
+            h.pf[(size_t)f * (K + 1) + i + 1] = h.pf[(size_t)f * (K + 1) + i] + (runs ? blocks : 0);
         };
-        add(F_FETCH, fetch[i] ? (int)(((int64_t)m * (d.ld / 16) + 255) / 256) : 0);
+        add(F_FETCH, g.fetch[i] ? (int)(((int64_t)m * (d.ld / 16) + 255) / 256) : 0);
         add(F_GAPS, (int)((d.ld / 4 + 255) / 256) * ((m + 63) / 64));
         add(F_ROWTOT, (m + 3) / 4);
         add(F_PLANES, ((d.nchunk + 1) / 2) * ((d.m_pad + 255) / 256));
         add(F_PAIRS, msak::pair_tiles_pipe(m, d.m_pad));
-        add(F_WMEANS, cols_mode ? 0 : (m + 64 + 3) / 4);  // (the predictor's input: the wave-per-column kernel only)
+        add(F_WMEANS, g.cols_mode ? 0 : (m + 64 + 3) / 4);  // (the predictor's input: the wave-per-column kernel only)
         add(F_IDROWS, d.gated ? (m + 3) / 4 : 0);
-        add(F_ENCODE, cols_mode ? (int)((d.ld + 255) / 256) * ((m + 15) / 16) : (d.ncols_pad / 64) * (int)(d.ldk / 64));
-        add(F_COMPACT, cols_mode ? 0 : (d.ncols_pad + 3) / 4);
+        add(F_ENCODE, g.cols_mode ? (int)((d.ld + 255) / 256) * ((m + 15) / 16) : (d.ncols_pad / 64) * (int)(d.ldk / 64));
+        add(F_COMPACT, g.cols_mode ? 0 : (d.ncols_pad + 3) / 4);
         add(F_FINISH, (n + 255) / 256);
-        add(F_COLS, cols_mode ? (n + 63) / 64 : n);
-        add(F_OVERLAP, d.kind == 3 ? (m + 3) / 4 : 0);
-        add(F_DIGEST, d.kind == 5 ? (m + 3) / 4 : 0);
+        add(F_COLS, g.cols_mode ? (n + 63) / 64 : n);
+        add(F_OVERLAP, it.kind == ENGINE_OVERLAP ? (m + 3) / 4 : 0);
+        add(F_DIGEST, it.kind == ENGINE_DIGESTS ? (m + 3) / 4 : 0);
     }
-    auto PF = [&](int f) { return pf_d + (size_t)f * (K + 1); };
-    auto NB = [&](int f) { return pf[(size_t)f * (K + 1) + K]; };
-    hipStream_t st = L.pre;
-    // zeroes: everything when the layout differs from the one the arena was last zeroed for (padding of W, of the rows:
-    // the kernels write the same entries for the same layout), else the result region alone (counts, flags)
-    if (sig != L.sig) {
-        HIPCHK(tc, hipMemsetAsync(A, 0, arena_bytes, st));
-        L.sig = sig;
-    } else {
-        HIPCHK(tc, hipMemsetAsync(A, 0, res_words * 4, st));
-    }
-    HIPCHK(tc, hipMemcpyAsync(meta_d, L.h_meta.p, meta_bytes, hipMemcpyHostToDevice, st));
-    if (stage_bytes) {
+}
+
+// The rows of the group into the arena on stream `st`: the packed ones through the staging buffer (one copy per run), the
+// direct ones in a copy each; the fetched ones are the first kernel's (engine_launch).
+static int engine_upload_rows(msa_batch *b, msa_ctx *tc, Engine::Lane &L, const EngineGroup &g, hipStream_t st) {
+    const BatchCall &c = b->call;
+    const int K = (int)L.items.size();
+    uint8_t *A = L.arena.p;
+    if (g.any_packed) {
         // pack (the calling thread and the idle workers), then one copy per run of packed alignments
         uint8_t *stage = L.h_stage.p;
         engine_parallel_for(b, K, [&](int32_t i, int) {
-            if (!packed[i]) return;
-            const int k = ks[i], m = b->m[k], n = b->n[k];
+            if (!g.packed[i]) return;
+            const int k = L.items[i].k, m = c.m[k], n = c.n[k];
             const size_t ld = round_up(n, 64);
-            const uint8_t *rows = b->data[k];
-            const int64_t hld = b->ld[k];
-            uint8_t *dst = stage + (lay[i].raw - raw_base);
+            const uint8_t *rows = c.data[k];
+            const int64_t hld = c.ld[k];
+            uint8_t *dst = stage + (g.lay[i].raw - g.raw_base);
             for (int r = 0; r < m; ++r) {
                 std::memcpy(dst + (size_t)r * ld, rows + (size_t)r * hld, (size_t)n);
                 std::memset(dst + (size_t)r * ld + n, 0, ld - n);
@@ -435,56 +469,111 @@ int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<i
         });
     }
     for (int i = 0; i < K; ++i) {
-        const int k = ks[i], m = b->m[k], n = b->n[k];
+        const int k = L.items[i].k, m = c.m[k], n = c.n[k];
         const size_t ld = round_up(n, 64);
-        if (fetch[i]) continue;
-        if (packed[i]) {
+        if (g.fetch[i]) continue;
+        if (g.packed[i]) {
             int j = i;
-            while (j + 1 < K && packed[j + 1]) ++j;
-            const size_t from = lay[i].raw, to = j + 1 < K ? lay[j + 1].raw : raw_base + raw_bytes;
-            HIPCHK(tc, hipMemcpyAsync(A + from, L.h_stage.p + (from - raw_base), to - from, hipMemcpyHostToDevice, st));
+            while (j + 1 < K && g.packed[j + 1]) ++j;
+            const size_t from = g.lay[i].raw, to = j + 1 < K ? g.lay[j + 1].raw : g.raw_base + g.raw_bytes;
+            HIPCHK(tc, hipMemcpyAsync(A + from, L.h_stage.p + (from - g.raw_base), to - from, hipMemcpyHostToDevice, st));
             i = j;
             continue;
         }
-        const uint8_t *rows = b->data[k];
-        const int64_t hld = b->ld[k];
-        uint8_t *dst = A + lay[i].raw;
+        const uint8_t *rows = c.data[k];
+        const int64_t hld = c.ld[k];
+        uint8_t *dst = A + g.lay[i].raw;
         if (hld == (int64_t)ld) HIPCHK(tc, hipMemcpyAsync(dst, rows, (size_t)m * ld, hipMemcpyHostToDevice, st));
         else HIPCHK(tc, hipMemcpy2DAsync(dst, ld, rows, (size_t)hld, (size_t)n, (size_t)m, hipMemcpyHostToDevice, st));
     }
-    msak::launch_fetch_rows_batch(st, bt_d, PF(F_FETCH), K, NB(F_FETCH));
-    msak::launch_gap_counts_batch(st, bt_d, PF(F_GAPS), K, NB(F_GAPS));
-    if (sort_cols) msak::launch_sort_columns_batch(st, bt_d, lt_d, K, max_m);
-    msak::launch_row_nongap_batch(st, bt_d, PF(F_ROWTOT), K, NB(F_ROWTOT));
-    msak::launch_overlap_rows_batch(st, bt_d, PF(F_OVERLAP), K, NB(F_OVERLAP));
-    msak::launch_row_digest_batch(st, bt_d, PF(F_DIGEST), K, NB(F_DIGEST));
-    msak::launch_prep_planes_batch(st, bt_d, PF(F_PLANES), K, NB(F_PLANES));
+    return MSA_OK;
+}
+
+// The launch sequence of a group -- one launch per kernel family on the lane's two queues -- and the one copy of its results
+// back.  `h` / `d`: the metadata as the host and the device see it.
+static int engine_launch(const BatchCall &c, msa_ctx *tc, Engine::Lane &L, const EngineGroup &g, const EngineMeta &h, const EngineMeta &d) {
+    const int K = (int)L.items.size();
+    auto PF = [&](int f) { return d.pf + (size_t)f * (K + 1); };
+    auto NB = [&](int f) { return h.pf[(size_t)f * (K + 1) + K]; };
+    hipStream_t st = L.pre;
+    msak::launch_fetch_rows_batch(st, d.bt, PF(F_FETCH), K, NB(F_FETCH));
+    msak::launch_gap_counts_batch(st, d.bt, PF(F_GAPS), K, NB(F_GAPS));
+    if (g.sort_cols) msak::launch_sort_columns_batch(st, d.bt, d.lt, K, g.max_m);
+    msak::launch_row_nongap_batch(st, d.bt, PF(F_ROWTOT), K, NB(F_ROWTOT));
+    msak::launch_overlap_rows_batch(st, d.bt, PF(F_OVERLAP), K, NB(F_OVERLAP));
+    msak::launch_row_digest_batch(st, d.bt, PF(F_DIGEST), K, NB(F_DIGEST));
+    msak::launch_prep_planes_batch(st, d.bt, PF(F_PLANES), K, NB(F_PLANES));
     int min_nchunk = 1 << 30;
-    for (int i = 0; i < K; ++i) {
-        const int kind = engine_needs(b->params + ks[i]);
-        if (kind == 2 || kind == 4) min_nchunk = std::min(min_nchunk, (b->n[ks[i]] + 31) / 32);
-    }
-    msak::launch_pair_counts_batch(st, bt_d, PF(F_PAIRS), K, NB(F_PAIRS), min_nchunk);
-    msak::launch_w_row_means_batch(st, bt_d, PF(F_WMEANS), K, NB(F_WMEANS));
-    msak::launch_identity_stats_batch(st, bt_d, PF(F_IDROWS), K, NB(F_IDROWS));
-    const int npos = any_sim >= 0 ? b->params[ks[any_sim]].npos : 0;
-    if (cols_mode) msak::launch_sim_encode_rm_batch(st, bt_d, PF(F_ENCODE), K, NB(F_ENCODE), tc->lut.p);
-    else msak::launch_sim_lists_batch(st, bt_d, PF(F_ENCODE), NB(F_ENCODE), PF(F_COMPACT), NB(F_COMPACT), K, tc->lut.p, npos);
+    for (const Engine::Item &it : L.items)
+        if (it.kind == ENGINE_SIMILARITY || it.kind == ENGINE_REPRESENTATIVE) min_nchunk = std::min(min_nchunk, (c.n[it.k] + 31) / 32);
+    msak::launch_pair_counts_batch(st, d.bt, PF(F_PAIRS), K, NB(F_PAIRS), min_nchunk);
+    msak::launch_w_row_means_batch(st, d.bt, PF(F_WMEANS), K, NB(F_WMEANS));
+    msak::launch_identity_stats_batch(st, d.bt, PF(F_IDROWS), K, NB(F_IDROWS));
+    const int npos = g.any_sim >= 0 ? c.params[L.items[g.any_sim].k].npos : 0;
+    if (g.cols_mode) msak::launch_sim_encode_rm_batch(st, d.bt, PF(F_ENCODE), K, NB(F_ENCODE), tc->lut.p);
+    else msak::launch_sim_lists_batch(st, d.bt, PF(F_ENCODE), NB(F_ENCODE), PF(F_COMPACT), NB(F_COMPACT), K, tc->lut.p, npos);
     HIPCHK(tc, hipEventRecord(L.prepared, st));
     st = L.stream;
     HIPCHK(tc, hipStreamWaitEvent(st, L.prepared, 0));
-    if (cols_mode) {
-        msak::launch_similarity_cols_batch(st, bt_d, PF(F_COLS), K, NB(F_COLS), tc->tab.p);
+    if (g.cols_mode) {
+        msak::launch_similarity_cols_batch(st, d.bt, PF(F_COLS), K, NB(F_COLS), tc->tab.p);
     } else {
         int launches = 0;
-        const int er = msak::launch_similarity_lg_batch(st, lt_d, PF(F_COLS), K, NB(F_COLS), max_m, npos, tc->tab.p, multi, &launches);
+        const int er = msak::launch_similarity_lg_batch(st, d.lt, PF(F_COLS), K, NB(F_COLS), g.max_m, npos, tc->tab.p, g.multi, &launches);
         if (er) return fail_hip(tc, (hipError_t)er, "launch_similarity (batch)");
     }
-    msak::launch_sim_finish_batch(st, bt_d, PF(F_FINISH), K, NB(F_FINISH));
+    msak::launch_sim_finish_batch(st, d.bt, PF(F_FINISH), K, NB(F_FINISH));
     HIPCHK(tc, hipGetLastError());
-    HIPCHK(tc, hipMemcpyAsync(L.h_res.p, A, res_words * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(tc, hipMemcpyAsync(L.h_res.p, L.arena.p, g.res_words * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(tc, hipEventRecord(L.done, st));
-    L.res_words = res_words;
+    return MSA_OK;
+}
+
+// one group on lane L: layout, tables, uploads, launches; engine_finish waits for it
+int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<Engine::Item> &group) {
+    const BatchCall &c = b->call;
+    msa_ctx *tc = e->tables;
+    const int K = (int)group.size();
+    if (!L.stream) {
+        int least = 0, greatest = 0;
+        HIPCHK(tc, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(tc, hipStreamCreateWithPriority(&L.pre, hipStreamNonBlocking, greatest));
+        HIPCHK(tc, hipStreamCreateWithPriority(&L.stream, hipStreamNonBlocking, least));
+        HIPCHK(tc, hipEventCreateWithFlags(&L.prepared, hipEventDisableTiming));
+        HIPCHK(tc, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+    }
+    L.items = group;
+    EngineGroup g = engine_layout(c, e, L.items);
+    engine_row_routes(c, e, L.items, g);
+    HIPCHK(tc, L.arena.reserve(g.arena_bytes));
+    g.mix((uint64_t)(uintptr_t)L.arena.p);
+    const size_t meta_bytes = engine_meta_bytes(K);
+    HIPCHK(tc, L.meta.reserve(meta_bytes));
+    HIPCHK(tc, L.h_meta.reserve(meta_bytes));
+    HIPCHK(tc, L.h_res.reserve(g.res_words * 4 + 64));
+    if (g.any_packed) {
+        // (the staging mirrors the raw region.  A grown staging buffer starts as zeros: the runs copied out of it span the slack
+        // and the alignment gaps between the packed alignments, which only ever hold what the buffer held when it was allocated
+        // -- the arena's padding stays zero whatever way the rows arrive)
+        const size_t had = L.h_stage.cap;
+        HIPCHK(tc, L.h_stage.reserve(g.raw_bytes));
+        if (L.h_stage.cap != had) std::memset(L.h_stage.p, 0, L.h_stage.cap);
+    }
+    const EngineMeta h = engine_meta(L.h_meta.p, K), d = engine_meta(L.meta.p, K);
+    engine_tables(c, L, g, h);
+    hipStream_t st = L.pre;
+    // zeroes: everything when the layout differs from the one the arena was last zeroed for (padding of W, of the rows:
+    // the kernels write the same entries for the same layout), else the result region alone (counts, flags)
+    if (g.sig != L.sig) {
+        HIPCHK(tc, hipMemsetAsync(L.arena.p, 0, g.arena_bytes, st));
+        L.sig = g.sig;
+    } else {
+        HIPCHK(tc, hipMemsetAsync(L.arena.p, 0, g.res_words * 4, st));
+    }
+    HIPCHK(tc, hipMemcpyAsync(L.meta.p, L.h_meta.p, meta_bytes, hipMemcpyHostToDevice, st));
+    int rc = engine_upload_rows(b, tc, L, g, st);
+    if (rc == MSA_OK) rc = engine_launch(c, tc, L, g, h, d);
+    if (rc != MSA_OK) return rc;
     L.busy = true;
     return MSA_OK;
 }
@@ -492,12 +581,13 @@ int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<i
 // The selection decisions of one alignment of a finished group, on view `v` (trim_impl reads the statistics the group's
 // result copy brought back).
 void engine_select_item(msa_batch *b, Engine::Lane &L, const Engine::Item &it, msa_ctx *v) {
+    const BatchCall &c = b->call;
     int32_t *res = reinterpret_cast<int32_t *>(L.h_res.p);
-    const int k = it.k, m = b->m[k], n = b->n[k];
+    const int k = it.k, m = c.m[k], n = c.n[k];
     int32_t *flags = res + it.res_word;
-    v->m = m, v->n = n, v->indet = b->indet[k], v->ld = round_up(n, 64);
+    v->m = m, v->n = n, v->indet = c.indet[k], v->ld = round_up(n, 64);
     v->raw = L.arena.p;  // (never read through the view)
-    v->host_rows = b->data[k], v->host_ld = b->ld[k];
+    v->host_rows = c.data[k], v->host_ld = c.ld[k];
     v->h_flags.p = flags;
     v->h_gaps.assign(flags + 16, flags + 16 + n);
     v->h_indets.assign(flags + 16 + it.npad, flags + 16 + it.npad + n);
@@ -506,34 +596,26 @@ void engine_select_item(msa_batch *b, Engine::Lane &L, const Engine::Item &it, m
     v->h_f32.p = reinterpret_cast<float *>(flags + 16 + 2 * it.npad + it.mpad);
     v->pairflag_state = 2;
     v->have_gaps = true;
-    // what the trimmers that remove sequences read (engine_needs 3 - 5)
-    const int kind = engine_needs(b->params + k);
+    // what the trimmers that remove sequences read
     const int32_t *extra = res + it.extra_word;
     v->ov_valid = false;
     v->pref_ident = nullptr, v->pref_lengths = nullptr, v->pref_hashes = nullptr;
-    if (kind == 3) {  // Cleaner::calculateSpuriousVector's values, as overlap() derives them from the counts
+    if (it.kind == ENGINE_OVERLAP) {  // Cleaner::calculateSpuriousVector's values, as overlap() derives them from the counts
         v->ov_vals.resize(m);
         for (int i = 0; i < m; ++i) v->ov_vals[i] = static_cast<float>(extra[i]) / n;
-        v->ov_key = b->params[k].residue_overlap;
+        v->ov_key = c.params[k].residue_overlap;
         v->ov_valid = true;
         v->ov_colcnt = false;
-    } else if (kind == 4) {
+    } else if (it.kind == ENGINE_REPRESENTATIVE) {
         v->pref_ident = reinterpret_cast<const float *>(extra);
         v->ldw = round_up(m, 64);
-    } else if (kind == 5) {
+    } else if (it.kind == ENGINE_DIGESTS) {
         v->pref_lengths = extra;
         v->pref_hashes = reinterpret_cast<const unsigned long long *>(extra + it.mpad);
     }
     msa_trim_info local;
-    msa_trim_info *info = b->info ? b->info + k : &local;
-    int rc;
-    try {
-        rc = trim_impl(v, b->params + k, b->keep_res[k], b->keep_seq[k], info);
-    } catch (const std::bad_alloc &) {
-        rc = MSA_E_NOMEM;
-    } catch (...) {
-        rc = MSA_E_INVALID;
-    }
+    msa_trim_info *info = c.info ? c.info + k : &local;
+    const int rc = no_throw([&] { return trim_impl(v, c.params + k, c.keep_res[k], c.keep_seq[k], info); });
     if (rc == MSA_E_FALLBACK) {
         if (v->tuning.trace) std::fprintf(stderr, "[engine] alignment %d (%d x %d) needs the device again: ordinary context\n", k, m, n);
         std::lock_guard<std::mutex> lk(b->mu);
@@ -541,7 +623,7 @@ void engine_select_item(msa_batch *b, Engine::Lane &L, const Engine::Item &it, m
         return;
     }
     b->only_gaps[k] = v->only_gaps_rows;
-    b->rc[k] = rc;
+    c.rc[k] = rc;
     b->sel_finished[k] = 1;
 }
 
@@ -618,9 +700,10 @@ void engine_destroy(Engine *e) {
     delete e;
 }
 
-// the alignments of the call in flight that the engine takes (`ks`, largest first), in groups, two groups in flight
-int engine_run(msa_batch *b, const std::vector<int32_t> &ks) {
-    if (ks.empty()) return MSA_OK;
+// the engine's share of the call in flight (`share`, largest first), in groups, two groups in flight
+int engine_run(msa_batch *b, const std::vector<Engine::Item> &share) {
+    if (share.empty()) return MSA_OK;
+    const BatchCall &c = b->call;
     if (!b->engine) {
         Engine *e = new (std::nothrow) Engine();
         if (!e) return MSA_E_NOMEM;
@@ -646,38 +729,39 @@ int engine_run(msa_batch *b, const std::vector<int32_t> &ks) {
     HIPCHK(tc, hipSetDevice(b->device));
     TuneScope tune(tc);
     int rc = MSA_OK;
-    for (int32_t k : ks)
-        if (engine_needs(b->params + k) == 2) {  // the one set of tables of the call (engine_takes: every such alignment shares it)
-            const msa_trim_params *p0 = b->params + k;
-            tc->indet = b->indet[k];
+    for (const Engine::Item &it : share)
+        if (it.kind == ENGINE_SIMILARITY) {  // the one set of tables of the call (engine_takes: every such alignment shares it)
+            const msa_trim_params *p0 = c.params + it.k;
+            tc->indet = c.indet[it.k];
             if ((rc = ensure_tables(tc, p0->vhash, p0->dist, p0->npos))) return rc;
             break;
         }
     // groups: about a quarter of the call each (at least two groups in flight whenever there are two alignments), bounded
     // by the arena (~8 GB) and by 256 alignments
-    const int total = (int)ks.size();
+    const int total = (int)share.size();
     int parts = 4;
     const int target = std::max(1, std::min(256, (total + parts - 1) / parts));
-    std::vector<std::vector<int32_t>> groups;
+    std::vector<std::vector<Engine::Item>> groups;
     {
-        std::vector<int32_t> cur;
+        std::vector<Engine::Item> cur;
         double bytes = 0;
-        for (int32_t k : ks) {
-            const double need = (double)b->m[k] * b->m[k] * 12 + (double)msak::bx_cols_pad(b->n[k]) * msak::bx_ldk(b->m[k]) * 7 + (double)b->m[k] * b->n[k] * 2;
+        for (const Engine::Item &it : share) {
+            const int m = c.m[it.k], n = c.n[it.k];
+            const double need = (double)m * m * 12 + (double)msak::bx_cols_pad(n) * msak::bx_ldk(m) * 7 + (double)m * n * 2;
             // (a group is small alignments -- a lane per column -- or not: the kernels differ)
-            const bool turn = !cur.empty() && (b->m[cur.front()] <= e->cols_max_m) != (b->m[k] <= e->cols_max_m);
+            const bool turn = !cur.empty() && (c.m[cur.front().k] <= e->cols_max_m) != (m <= e->cols_max_m);
             if (!cur.empty() && ((int)cur.size() >= target || bytes + need > 8e9 || turn)) {
                 groups.push_back(cur);
                 cur.clear();
                 bytes = 0;
             }
-            cur.push_back(k);
+            cur.push_back(it);
             bytes += need;
         }
         if (!cur.empty()) groups.push_back(cur);
     }
     b->sel_redo.clear();
-    b->sel_finished.assign((size_t)b->count, 0);
+    b->sel_finished.assign((size_t)c.count, 0);
     const int G = (int)groups.size();
     int first_error = MSA_OK;
     for (int g = 0; g < G && first_error == MSA_OK; ++g) {
@@ -700,68 +784,88 @@ int engine_run(msa_batch *b, const std::vector<int32_t> &ks) {
             if (L.stream) (void)hipStreamSynchronize(L.stream);
             L.busy = false;
         }
-        for (int32_t k : ks)
-            if (!b->sel_finished[k]) b->rc[k] = first_error;  // (the groups that were through keep their results)
+        for (const Engine::Item &it : share)
+            if (!b->sel_finished[it.k]) c.rc[it.k] = first_error;  // (the groups that were through keep their results)
         return first_error;
     }
     // the selection of these needs another pass over the rows: an ordinary context
-    for (int32_t k : b->sel_redo) {
-        msa_trim_info local;
-        msa_trim_info *info = b->info ? b->info + k : &local;
-        rc = msa_upload_packed_async(tc, b->data[k], b->m[k], b->n[k], b->ld[k], b->indet[k]);
-        if (rc == MSA_OK) rc = msa_trim(tc, b->params + k, b->keep_res[k], b->keep_seq[k], info);
-        else (void)hipStreamSynchronize(tc->stream);
-        b->only_gaps[k] = tc->only_gaps_rows;
-        b->rc[k] = rc;
-    }
+    for (int32_t k : b->sel_redo) c.rc[k] = rows_item(b, tc, k);
     return MSA_OK;
 }
 
-}  // namespace msai
-
-namespace msai {
-// one text of msa_trim_batch_fasta on worker context c: parse, trim with the parameters of its type, names (and rows)
-int fasta_item(msa_batch *b, msa_ctx *c, int32_t k) {
-    msa_batch::FastaResult &r = b->fasta[k];
-    r.parse_rc = msa_upload_fasta(c, b->texts[k], b->lens[k], b->valid, &r.info, &r.detail);
-    const int m = r.info.m, n = r.info.n;
-    if (r.parse_rc != MSA_OK) {  // (a failure names its record: the names came with the parse)
-        if ((r.parse_rc == MSA_E_BAD_RESIDUE || r.parse_rc == MSA_E_LENGTH_MISMATCH) && m > 0) {
-            r.name_off.resize((size_t)m);
-            r.name_len.resize((size_t)m);
-            if (msa_text_names(c, r.name_off.data(), r.name_len.data()) != MSA_OK) r.name_off.clear(), r.name_len.clear();
+// Splits the call's alignments (`order`: all of them, largest first) into what the engine takes (batched kernels, the calling
+// thread; returned) and what the workers take (a context per alignment; left in `order`).
+static std::vector<Engine::Item> engine_share(msa_batch *b, std::vector<int32_t> &order) {
+    const BatchCall &c = b->call;
+    std::vector<Engine::Item> share;
+    std::vector<int32_t> rest;
+    const msa_trim_params *ref = nullptr;
+    for (int32_t k : order) {
+        const EngineKind kind = engine_takes(b, k, ref);
+        if (kind == ENGINE_NONE) {
+            rest.push_back(k);
+            continue;
         }
+        if (!ref && kind == ENGINE_SIMILARITY) ref = c.params + k;
+        share.push_back(Engine::Item{k, kind, 0, 0, 0, 0});
+    }
+    // A handful of small alignments is faster through the worker contexts (each a compact pipeline of three launches,
+    // compact_begin) than as a group of the batched kernels with its arena, tables and ten launches: 8 x (100 x 1000) 0.31
+    // against 0.96 ms, 16: 0.57 / 1.11, 32: 1.0 / 1.2, 64: 2.0 / 1.45 (tools/small_batch.py).
+    if ((int)share.size() < b->engine_min_count) {
+        for (const Engine::Item &it : share) rest.push_back(it.k);
+        std::stable_sort(rest.begin(), rest.end(), [&](int32_t x, int32_t y) {
+            return (double)c.m[x] * c.m[x] * c.n[x] > (double)c.m[y] * c.m[y] * c.n[y];
+        });
+        share.clear();
+    }
+    order.swap(rest);
+    return share;
+}
+
+// the index into params_by_type of a detected sequence type (SequenceTypes bits): amino acids and an undetected type 0,
+// nucleotides 1, degenerate nucleotides 2 -- the matrices the Python side picks by type (trimmer.type_index)
+static int seq_type_index(uint32_t ty) { return (ty & 4) || ty == 0 ? 0 : (ty & 8) ? 2 : 1; }
+
+// one text of a TEXTS call on worker context ctx: parse, trim with the parameters of its type, names (and rows, and the text)
+int fasta_item(msa_batch *b, msa_ctx *ctx, int32_t k) {
+    const BatchCall &c = b->call;
+    msa_batch::FastaResult &r = b->fasta[k];
+    ctx->only_gaps_rows.clear();
+    r.parse_rc = msa_upload_fasta(ctx, c.texts[k], c.lens[k], c.valid, &r.info, &r.detail);
+    const int m = r.info.m, n = r.info.n;
+    auto names = [&] {  // the records' names, as (offset, length) into the text
+        r.name_off.resize((size_t)m);
+        r.name_len.resize((size_t)m);
+        return msa_text_names(ctx, r.name_off.data(), r.name_len.data());
+    };
+    if (r.parse_rc != MSA_OK) {  // (a failure names its record: the names came with the parse)
+        if ((r.parse_rc == MSA_E_BAD_RESIDUE || r.parse_rc == MSA_E_LENGTH_MISMATCH) && m > 0 && names() != MSA_OK) r.name_off.clear(), r.name_len.clear();
         return r.parse_rc;
     }
-    const uint32_t ty = r.info.seq_type;
     r.keep_res.assign((size_t)n, 1);
     r.keep_seq.assign((size_t)m, 1);
     int rc = MSA_OK;
     if (m > 0 && n > 0) {  // (an empty alignment never reaches the device: trim_batch)
-        const msa_trim_params *p = b->params_by_type + ((ty & 4) || ty == 0 ? 0 : ((ty & 8) ? 2 : 1));
-        rc = msa_trim(c, p, r.keep_res.data(), r.keep_seq.data(), &r.tinfo);
-        b->only_gaps[k] = c->only_gaps_rows;
-        if (rc == MSA_OK && b->want_rows) {
+        rc = msa_trim(ctx, c.params_by_type + seq_type_index(r.info.seq_type), r.keep_res.data(), r.keep_seq.data(), &r.tinfo);
+        b->only_gaps[k] = ctx->only_gaps_rows;
+        if (rc == MSA_OK && c.want_rows) {
             r.rows.resize((size_t)m * n);
-            rc = msa_download_rows(c, r.rows.data(), n);
+            rc = msa_download_rows(ctx, r.rows.data(), n);
         }
-        if (rc == MSA_OK && b->emit_format >= 0) {  // the trimmed text, composed under the masks of this trim with the text's own names
+        if (rc == MSA_OK && c.emit_format >= 0) {  // the trimmed text, composed under the masks of this trim with the text's own names
             int64_t len = 0;
-            const int erc = msa_emit_text(c, b->emit_format, r.keep_res.data(), r.keep_seq.data(), nullptr, nullptr, nullptr, &len, &r.text_flags);
+            const int erc = msa_emit_text(ctx, c.emit_format, r.keep_res.data(), r.keep_seq.data(), nullptr, nullptr, nullptr, &len, &r.text_flags);
             if (erc == MSA_OK && !r.text_flags) {
                 r.text.reset(new uint8_t[(size_t)std::max<int64_t>(len, 1)]);
-                if ((rc = msa_download_text(c, r.text.get(), len)) == MSA_OK) r.text_len = len;
+                if ((rc = msa_download_text(ctx, r.text.get(), len)) == MSA_OK) r.text_len = len;
                 else r.text.reset();
             } else if (erc != MSA_OK && !(r.text_flags & MSA_TEXT_F_TOO_LONG)) {
                 rc = erc;  // (a text too long for the device is the caller's to write: the flag says so, the trim stands)
             }
         }
     }
-    if (rc == MSA_OK && m > 0) {
-        r.name_off.resize((size_t)m);
-        r.name_len.resize((size_t)m);
-        rc = msa_text_names(c, r.name_off.data(), r.name_len.data());
-    }
+    if (rc == MSA_OK && m > 0) rc = names();
     return rc;
 }
 
@@ -789,41 +893,73 @@ void batch_worker(msa_batch *b, int w) {
             if (--b->sel_active == 0) b->cv_done.notify_all();
             continue;
         }
-        msa_ctx *c = b->ctxs[w];
+        const BatchCall &c = b->call;
+        msa_ctx *ctx = b->ctxs[w];
         for (;;) {
             const int32_t slot = b->next.fetch_add(1, std::memory_order_relaxed);
             if (slot >= (int32_t)b->order.size()) break;
             const int32_t k = b->order[slot];
-            msa_trim_info local;
-            msa_trim_info *info = b->info ? b->info + k : &local;
-            int rc;
-            try {  // (an exception must not leave the thread: std::terminate would take the caller's process with it)
-                c->only_gaps_rows.clear();
-                if (b->texts) rc = fasta_item(b, c, k);
-                else if ((rc = msa_upload_packed_async(c, b->data[k], b->m[k], b->n[k], b->ld[k], b->indet[k])) == MSA_OK)
-                    rc = msa_trim(c, b->params + k, b->keep_res[k], b->keep_seq[k], info);
-                else {
-                    std::memset(info, 0, sizeof(*info));
-                    (void)hipStreamSynchronize(c->stream);  // (nothing of a failed upload may stay in flight over the caller's rows)
-                }
-                b->only_gaps[k] = c->only_gaps_rows;
-            } catch (const std::bad_alloc &) {
-                rc = MSA_E_NOMEM;
-            } catch (...) {
-                rc = MSA_E_INVALID;
-            }
+            const int rc = no_throw([&] { return c.kind == BatchCall::TEXTS ? fasta_item(b, ctx, k) : rows_item(b, ctx, k); });
             if (rc == MSA_E_NOMEM || rc == MSA_E_INVALID) {
-                if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-                (void)hipStreamSynchronize(c->stream);
-                c->upload_pending = false;
+                if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+                (void)hipStreamSynchronize(ctx->stream);
+                ctx->upload_pending = false;
             }
-            b->rc[k] = rc;
+            c.rc[k] = rc;
         }
         {
             std::lock_guard<std::mutex> lk(b->mu);
             if (--b->running == 0) b->cv_done.notify_all();
         }
     }
+}
+
+// The protocol of every call, of either kind: refuse a second call, take `call`, order its alignments largest first (`key`),
+// hand the workers their share, run the engine's share (ROWS only) on the calling thread, wait for the workers, clear the
+// call, return the first failure.
+template <class Key>
+static int run_call(msa_batch *b, const BatchCall &call, Key key) {
+    const int32_t count = call.count;
+    if (count == 0) return MSA_OK;
+    const bool rows = call.kind == BatchCall::ROWS;
+    std::vector<Engine::Item> share;
+    {
+        std::unique_lock<std::mutex> lk(b->mu);
+        if (b->running || b->in_call) return MSA_E_INVALID;  // one call at a time per batch object
+        b->in_call = true;
+        b->call = call;
+        // largest first: the last alignments to finish are the small ones
+        b->order.resize(count);
+        for (int32_t k = 0; k < count; ++k) b->order[k] = k;
+        std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return key(x) > key(y); });
+        if (rows && b->use_engine) share = engine_share(b, b->order);
+        // what the last call left behind goes now (msa_batch_fasta_result, msa_batch_only_gaps_rows: results of the last call only)
+        b->only_gaps.assign(count, {});
+        b->fasta.clear();
+        if (!rows) b->fasta.resize((size_t)count);
+        for (int32_t k = 0; k < count; ++k) call.rc[k] = MSA_OK;
+        b->next.store(0);
+        b->running = b->order.empty() ? 0 : (int)b->workers.size();
+        if (b->running) ++b->generation;
+    }
+    if (!b->order.empty()) b->cv_work.notify_all();
+    const auto t_call = std::chrono::steady_clock::now();
+    const int engine_rc = no_throw([&] { return engine_run(b, share); });
+    if (engine_rc != MSA_OK)
+        for (const Engine::Item &it : share)
+            if (call.rc[it.k] == MSA_OK && !(it.k < (int32_t)b->sel_finished.size() && b->sel_finished[it.k])) call.rc[it.k] = engine_rc;
+    {
+        std::unique_lock<std::mutex> lk(b->mu);
+        b->cv_done.wait(lk, [&] { return b->running == 0; });
+        b->in_call = false;
+        b->call = BatchCall();
+    }
+    if (rows && std::getenv("MSA_TRACE"))
+        std::fprintf(stderr, "[msa_trim_batch] %d alignments: %zu through the batched kernels, %zu through the workers, %.2f ms\n", (int)count,
+                     share.size(), b->order.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+    for (int32_t k = 0; k < count; ++k)
+        if (call.rc[k] != MSA_OK) return call.rc[k];
+    return MSA_OK;
 }
 }  // namespace msai
 
@@ -875,111 +1011,21 @@ int msa_trim_batch(msa_batch *b, int32_t count, const uint8_t *const *data, cons
                    msa_trim_info *info, int32_t *rc) {
     if (!b || count < 0 || (count > 0 && (!data || !m || !n || !ld || !indet || !params || !keep_res || !keep_seq || !rc)))
         return MSA_E_INVALID;
-    if (count == 0) return MSA_OK;
-    std::vector<int32_t> engine_ks;
-    {
-        std::unique_lock<std::mutex> lk(b->mu);
-        if (b->running || b->in_call) return MSA_E_INVALID;  // one call at a time per batch object
-        b->in_call = true;
-        b->count = count;
-        b->data = data, b->m = m, b->n = n, b->ld = ld, b->indet = indet, b->params = params;
-        b->keep_res = keep_res, b->keep_seq = keep_seq, b->info = info, b->rc = rc;
-        // largest first (cost ~ m^2 n): the last alignments to finish are the small ones.  What the engine takes (batched
-        // kernels, this thread) and what the workers take (a context per alignment)
-        std::vector<int32_t> all(count);
-        for (int32_t k = 0; k < count; ++k) all[k] = k;
-        std::stable_sort(all.begin(), all.end(), [&](int32_t x, int32_t y) {
-            return (double)m[x] * m[x] * n[x] > (double)m[y] * m[y] * n[y];
-        });
-        b->order.clear();
-        const msa_trim_params *ref = nullptr;
-        for (int32_t k : all) {
-            if (b->use_engine && engine_takes(b, k, ref)) {
-                if (!ref && engine_needs(params + k) == 2) ref = params + k;
-                engine_ks.push_back(k);
-            } else {
-                b->order.push_back(k);
-            }
-        }
-        // A handful of small alignments is faster through the worker contexts (each a compact pipeline of three launches,
-        // compact_begin) than as a group of the batched kernels with its arena, tables and ten launches: 8 x (100 x 1000) 0.31
-        // against 0.96 ms, 16: 0.57 / 1.11, 32: 1.0 / 1.2, 64: 2.0 / 1.45 (tools/small_batch.py).
-        if ((int)engine_ks.size() < b->engine_min_count) {
-            b->order.insert(b->order.end(), engine_ks.begin(), engine_ks.end());
-            std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) {
-                return (double)m[x] * m[x] * n[x] > (double)m[y] * m[y] * n[y];
-            });
-            engine_ks.clear();
-        }
-        b->only_gaps.assign(count, {});
-        b->fasta.clear();  // (msa_batch_fasta_result: results of the last call only)
-        for (int32_t k = 0; k < count; ++k) rc[k] = MSA_OK;
-        b->next.store(0);
-        b->running = b->order.empty() ? 0 : (int)b->workers.size();
-        if (b->running) ++b->generation;
-    }
-    if (!b->order.empty()) b->cv_work.notify_all();
-    const auto t_call = std::chrono::steady_clock::now();
-    int engine_rc = MSA_OK;
-    try {
-        engine_rc = engine_run(b, engine_ks);
-    } catch (const std::bad_alloc &) {
-        engine_rc = MSA_E_NOMEM;
-    } catch (...) {
-        engine_rc = MSA_E_INVALID;
-    }
-    if (engine_rc != MSA_OK)
-        for (int32_t k : engine_ks)
-            if (rc[k] == MSA_OK && !(k < (int32_t)b->sel_finished.size() && b->sel_finished[k])) rc[k] = engine_rc;
-    {
-        std::unique_lock<std::mutex> lk(b->mu);
-        b->cv_done.wait(lk, [&] { return b->running == 0; });
-    }
-    {
-        std::lock_guard<std::mutex> lk(b->mu);
-        b->in_call = false;
-    }
-    if (std::getenv("MSA_TRACE"))
-        std::fprintf(stderr, "[msa_trim_batch] %d alignments: %zu through the batched kernels, %zu through the workers, %.2f ms\n", (int)count,
-                     engine_ks.size(), b->order.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
-    for (int32_t k = 0; k < count; ++k)
-        if (rc[k] != MSA_OK) return rc[k];
-    return MSA_OK;
+    BatchCall call;
+    call.kind = BatchCall::ROWS, call.count = count, call.rc = rc;
+    call.data = data, call.m = m, call.n = n, call.ld = ld, call.indet = indet, call.params = params;
+    call.keep_res = keep_res, call.keep_seq = keep_seq, call.info = info;
+    return run_call(b, call, [&](int32_t k) { return (double)m[k] * m[k] * n[k]; });  // (cost ~ m^2 n)
 }
 
 static int trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
                             const msa_trim_params params_by_type[3], int32_t want_rows, int32_t format, int32_t *rc) {
     if (!b || count < 0 || (count > 0 && (!texts || !lens || !params_by_type || !rc))) return MSA_E_INVALID;
-    if (count == 0) return MSA_OK;
-    {
-        std::unique_lock<std::mutex> lk(b->mu);
-        if (b->running || b->in_call) return MSA_E_INVALID;  // one call at a time per batch object
-        b->in_call = true;
-        b->count = count;
-        b->texts = texts, b->lens = lens, b->valid = valid, b->params_by_type = params_by_type, b->want_rows = want_rows != 0;
-        b->emit_format = format;
-        b->info = nullptr, b->rc = rc;
-        b->order.resize(count);
-        for (int32_t k = 0; k < count; ++k) b->order[k] = k;
-        std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return lens[x] > lens[y]; });  // largest first
-        b->fasta.clear();
-        b->fasta.resize((size_t)count);
-        b->only_gaps.assign(count, {});
-        for (int32_t k = 0; k < count; ++k) rc[k] = MSA_OK;
-        b->next.store(0);
-        b->running = (int)b->workers.size();
-        ++b->generation;
-    }
-    b->cv_work.notify_all();
-    {
-        std::unique_lock<std::mutex> lk(b->mu);
-        b->cv_done.wait(lk, [&] { return b->running == 0; });
-        b->in_call = false;
-        b->texts = nullptr;
-    }
-    for (int32_t k = 0; k < count; ++k)
-        if (rc[k] != MSA_OK) return rc[k];
-    return MSA_OK;
+    BatchCall call;
+    call.kind = BatchCall::TEXTS, call.count = count, call.rc = rc;
+    call.texts = texts, call.lens = lens, call.valid = valid, call.params_by_type = params_by_type;
+    call.want_rows = want_rows != 0, call.emit_format = format;
+    return run_call(b, call, [&](int32_t k) { return lens[k]; });
 }
 
 int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
@@ -1030,4 +1076,3 @@ const char *msa_batch_last_hip_error(const msa_batch *b, int32_t worker) {
 }
 
 }  // extern "C"
-

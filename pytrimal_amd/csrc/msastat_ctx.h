@@ -381,5 +381,15 @@ int compact_overlap(msa_ctx *c, float residue_overlap, float sequence_overlap);
 int compact_begin(msa_ctx *c, const int32_t *vhash, const float *dist, int npos, bool gated);
 int trim_impl(msa_ctx *c, const msa_trim_params *p, uint8_t *keep_res, uint8_t *keep_seq, msa_trim_info *info);
 // msastat_batch.hip
-int engine_needs(const msa_trim_params *p);
+// What a trim needs of the device, as msa_trim_batch's engine sees it.  The values are those of the device-side BAlign::kind
+// (msastat_kernels.h): the batched kernels read them.
+enum EngineKind : int32_t {
+    ENGINE_NONE = 0,            // not a trim the engine knows
+    ENGINE_GAPS = 1,            // the gap statistics alone (gappyout, nogaps, noallgaps, a manual gap threshold)
+    ENGINE_SIMILARITY = 2,      // the similarity pipeline as well
+    ENGINE_OVERLAP = 3,         // OverlapTrimmer: the overlap counts of every sequence
+    ENGINE_REPRESENTATIVE = 4,  // RepresentativeTrimmer: the identities
+    ENGINE_DIGESTS = 5,         // noduplicateseqs: row digests
+};
+EngineKind engine_needs(const msa_trim_params *p);
 }  // namespace msai

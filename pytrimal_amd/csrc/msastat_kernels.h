@@ -144,7 +144,7 @@ struct BAlign {
     int32_t m, n, nchunk, m_pad, ldw, ncols_pad;
     uint32_t indet4;
     int32_t gated;            // automated1: the identity statistics decide on the device whether the similarity values are needed
-    // what the alignment's trim needs of the device (msa_trim_batch's engine: engine_needs): 1 the gap statistics alone, 2 the
+    // what the alignment's trim needs of the device (msa_trim_batch's engine: EngineKind, msastat_ctx.h): 1 the gap statistics alone, 2 the
     // similarity pipeline, 3 OverlapTrimmer's counts as well (ov_need, -> extra[m]), 4 the identities (ident points into the
     // result region: RepresentativeTrimmer clusters on the host-only view), 5 row digests (noduplicateseqs: extra = lengths
     // [round_up(m + 64, 64)], then two 64-bit hashes per row)

@@ -445,8 +445,8 @@ int trim_impl(msa_ctx *c, const msa_trim_params *p, uint8_t *keep_res, uint8_t *
     if (c->prefetched) {
         // (what the engine takes: the similarity pipeline without a gap window, a trim that needs the gap statistics alone, the
         // trimmers that remove sequences -- their statistics are in the view: engine_needs)
-        const int kind = engine_needs(p);
-        if ((int)c->h_gaps.size() != n || !((pipelined && gap_hw == 0) || kind == 1 || kind >= 3)) return MSA_E_FALLBACK;
+        const EngineKind kind = engine_needs(p);
+        if ((int)c->h_gaps.size() != n || !((pipelined && gap_hw == 0) || (kind != ENGINE_NONE && kind != ENGINE_SIMILARITY))) return MSA_E_FALLBACK;
         gaps_w.resize(n);
         if ((rc = msah::window_i32(c->h_gaps.data(), n, gap_hw, gaps_w.data()))) return rc;
         c->pipe_active = pipelined;

@@ -27,6 +27,23 @@ def _default_matrix(kind):
     return SimilarityMatrix.nt(degenerated=(kind == "ntdeg"))
 
 
+_TYPE_KINDS = ("aa", "nt", "ntdeg")
+
+
+def type_index(ty):
+    """A detected sequence type (trimAl's SequenceTypes bits) -> 0 amino acids, 1 nucleotides, 2 degenerate nucleotides: the
+    default matrix of the type (create_or_use_similarity_matrix; an undetected type falls back to the AA matrix,
+    _trimal.pyx:1342-1352) and the order of `_fasta_params` (the library's `seq_type_index` is the same rule)."""
+    return 0 if (ty & 4 or ty == 0) else (2 if ty & 8 else 1)
+
+
+def computes_gap_stats(params):
+    """Does a trim with this parameter block compute gap statistics (every column trimmer does; the sequence trimmers do not)?
+    `terminal_only` shares them with the source alignment when it did, and counts over the kept sequences when it did not."""
+    return (params.method != _lib.METHOD_CODES["noduplicateseqs"] and params.clusters == -1 and params.max_identity == -1
+            and not (params.residue_overlap != -1 and params.sequence_overlap != -1))
+
+
 @functools.lru_cache(maxsize=None)
 def _best_platform():
     """"hip" when a device is visible, else `None`.  Resolved on first use (a trimmer is constructed), never at
@@ -149,13 +166,15 @@ class BaseTrimmer:
         ty = alignment._alignment_type()
         indet = ord("X") if (ty & 4) else ord("N")
         if matrix is None:
-            # create_or_use_similarity_matrix; an undetected type falls back to the AA matrix (:1342-1352)
-            if ty & 4 or ty == 0:
-                matrix = _default_matrix("aa")
-            else:
-                matrix = _default_matrix("ntdeg" if ty & 8 else "nt")
+            matrix = _default_matrix(_TYPE_KINDS[type_index(ty)])
         params, keep = self._params_for(matrix)
         return alignment.names, dense, indet, params, keep
+
+    def _template(self):
+        """This trimmer's parameter block, without a matrix."""
+        template = _lib.TrimParams(0, -1.0, -1, -1.0, -1.0, -1, -1, -1, -1.0, -1.0, -1, -1.0, None, None, 0)
+        self._configure(template)
+        return template
 
     def _params_for(self, matrix):
         """The parameter block of this trimmer for `matrix` and the objects it points into."""
@@ -167,8 +186,7 @@ class BaseTrimmer:
         key = (id(matrix), tuple(self.__getstate__().items()))
         entry = cache.get(key)
         if entry is None or entry[2] is not matrix:
-            template = _lib.TrimParams(0, -1.0, -1, -1.0, -1.0, -1, -1, -1, -1.0, -1.0, -1, -1.0, None, None, 0)
-            self._configure(template)
+            template = self._template()
             vhash, dist = matrix._device_arrays()
             template.vhash = vhash.ctypes.data_as(ctypes.c_void_p)
             template.dist = dist.ctypes.data_as(ctypes.c_void_p)
@@ -182,7 +200,7 @@ class BaseTrimmer:
         """The three parameter blocks of `msa_trim_batch_fasta` -- amino acids (and an undetected type), nucleotides,
         degenerate nucleotides: the matrices `_prepare` picks by type.  (`matrix`: None or a SimilarityMatrix; the caller
         has checked it and the platform, as `_prepare` does.)"""
-        kinds = (matrix,) * 3 if matrix is not None else tuple(_default_matrix(k) for k in ("aa", "nt", "ntdeg"))
+        kinds = (matrix,) * 3 if matrix is not None else tuple(_default_matrix(k) for k in _TYPE_KINDS)
         out, keep = (_lib.TrimParams * 3)(), []
         for i, mx in enumerate(kinds):
             out[i], k = self._params_for(mx)
@@ -199,10 +217,7 @@ class BaseTrimmer:
         # statistics object of its source): the half window, and the windowed vector itself when the trim fetched it
         out._gap_hw = max(params.window if params.window != -1 else params.gap_window, 0)
         out._gaps_w = gaps_w
-        # did this trim compute gap statistics (every column trimmer does; the sequence trimmers do not)?  `terminal_only`
-        # shares them with the source alignment when it did, and counts over the kept sequences when it did not
-        out._gap_stats = (params.method != _lib.METHOD_CODES["noduplicateseqs"] and params.clusters == -1 and params.max_identity == -1
-                          and not (params.residue_overlap != -1 and params.sequence_overlap != -1))
+        out._gap_stats = computes_gap_stats(params)
         return out
 
     def trim(self, alignment, matrix=None):

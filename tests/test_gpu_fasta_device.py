@@ -371,3 +371,45 @@ def test_fasta_results_belong_to_the_last_call(tmp_path):
     assert b.lib.msa_batch_fasta_result(b.h, 0, None, None, None, None, None, None, None, None) == _lib.OK
     trim_batch(t, [Alignment.load(str(path))], shard=False, masks_only=True)
     assert b.lib.msa_batch_fasta_result(b.h, 0, None, None, None, None, None, None, None, None) == _lib.E_INVALID
+
+
+def test_nothing_of_a_call_survives_into_the_next_kind_of_call():
+    """a rows call after a text call with `emit` and `want_rows`, and a text call after a rows call, on one batch object:
+    the masks fresh batch objects give, and no rows or text that only the earlier call asked for"""
+    shapes = [(30, 120, "protein"), (25, 200, "dna"), (12, 90, "deg"), (40, 300, "protein")]
+    texts = [synth_text(m, n, 40 + k, kind) for k, (m, n, kind) in enumerate(shapes)]
+    t = ManualTrimmer(gap_threshold=0.7, similarity_threshold=0.3)
+    params3, _keep = t._fasta_params(None)
+    items = [t._prepare(Alignment.load(io.BytesIO(x), "fasta"))[1:4] for x in texts]
+
+    def rows_call(b):
+        outs = b.trim(items)
+        assert [o[3] for o in outs] == [_lib.OK] * len(items)
+        return [(o[0].copy(), o[1].copy()) for o in outs]
+
+    def text_call(b, **kw):
+        recs = b.trim_fasta(texts, _VALID.view(np.uint8), params3, **kw)
+        assert [(r.parse_rc, r.rc) for r in recs] == [(_lib.OK, _lib.OK)] * len(texts)
+        return recs
+
+    def same(got, want):
+        return len(got) == len(want) and all(np.array_equal(g[0], w[0]) and np.array_equal(g[1], w[1]) for g, w in zip(got, want))
+
+    fresh = _lib.Batch(None, 3)
+    want_rows = rows_call(fresh)
+    fresh.close()
+    fresh = _lib.Batch(None, 3)
+    want_text = [(r.keep_res, r.keep_seq) for r in text_call(fresh)]
+    fresh.close()
+    assert not all(res.all() for res, _ in want_rows)  # (the trim removes something)
+    b = _lib.Batch(None, 3)
+    try:
+        first = text_call(b, want_rows=True, emit="clustal")
+        assert all(r.rows is not None and r.text for r in first)
+        assert same(rows_call(b), want_rows)
+        after = text_call(b)
+        assert same([(r.keep_res, r.keep_seq) for r in after], want_text)
+        assert all(r.rows is None and r.text is None for r in after)
+        assert same(rows_call(b), want_rows)
+    finally:
+        b.close()

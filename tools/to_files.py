@@ -32,6 +32,7 @@ import torch  # noqa: F401,E402  (before the HIP library: see pytrimal_amd._lib)
 
 from pytrimal_amd import Alignment, AutomaticTrimmer, _lib  # noqa: E402
 from pytrimal_amd.batch import trim_files  # noqa: E402
+from pytrimal_amd.trimmer import type_index  # noqa: E402
 from from_files import timed, write_set  # noqa: E402  (tools/ is the script's directory)
 
 
@@ -100,8 +101,7 @@ def one_text_case(path, trimmer, warmup, repeats):
 
     def device_route():
         info = ctx.upload_fasta(text)
-        ty = info.seq_type
-        res, seq, _ = ctx.trim(params[0 if (ty & 4 or ty == 0) else (2 if ty & 8 else 1)])
+        res, seq, _ = ctx.trim(params[type_index(info.seq_type)])
         state["masks"] = (res, seq)
         state["device"] = ctx.emit_text("fasta", res, seq)
 
