@@ -373,6 +373,33 @@ enum {
 enum { MSA_PATH_PAIRS_NONE = 0, MSA_PATH_PAIRS_PIPE = 1 /* one row j per lane */, MSA_PATH_PAIRS_TWO_ROWS = 2 /* two rows j per lane */,
        MSA_PATH_PAIRS_PIPE16 = 3 /* one row j per lane, sixteen rows i per tile (up to 1024 sequences) */ };
 int msa_debug_last_paths(msa_ctx *ctx, int32_t out[8]);
+/* Which way every alignment of the batch object's last msa_trim_batch went (diagnostics, like msa_debug_last_paths: it changes
+ * nothing that is computed, and tests/test_gpu_batch_engine.py asserts it): writes at most cap entries of route[], one per
+ * alignment of that call in the call's order, and returns their number (0 after a call for texts; MSA_E_INVALID for a NULL
+ * handle or while a call is in flight).  An entry is 0 for an alignment a worker context took (its own msa_upload_packed_async +
+ * msa_trim), else MSA_ROUTE_ENGINE with
+ *   - MSA_ROUTE_LANE_PER_COLUMN: its similarity statistic ran with a lane per column (a group of alignments of up to 128 rows);
+ *   - MSA_ROUTE_SEVERAL_LAUNCHES: ... in the wave-per-column kernel's several launches with per-column state (a group whose
+ *     tallest similarity trim has 1800 rows or more); neither bit: that kernel in one launch, or no similarity statistic at all;
+ *   - MSA_ROUTE_SELECTION_REDONE: the selection on the group's results needed the rows again and an ordinary context trimmed it;
+ *   - (entry >> MSA_ROUTE_ROWS_SHIFT) & MSA_ROUTE_ROWS_MASK: how its rows reached the group's arena (MSA_ROUTE_ROWS_*);
+ *   - entry >> MSA_ROUTE_GROUP_SHIFT: the index of its group in the call (groups g and g + 2 share a lane and its arena). */
+enum {
+    MSA_ROUTE_ENGINE = 1 << 0,
+    MSA_ROUTE_LANE_PER_COLUMN = 1 << 1,
+    MSA_ROUTE_SEVERAL_LAUNCHES = 1 << 2,
+    MSA_ROUTE_SELECTION_REDONE = 1 << 3,
+    MSA_ROUTE_ROWS_SHIFT = 4,
+    MSA_ROUTE_ROWS_MASK = 7,
+    MSA_ROUTE_GROUP_SHIFT = 8
+};
+enum {
+    MSA_ROUTE_ROWS_LINEAR = 1,  /* rows already 64-byte padded rows apart: one linear copy */
+    MSA_ROUTE_ROWS_COPY_2D = 2, /* one pitched copy straight from the caller's rows (16-byte aligned, or page-locked and big) */
+    MSA_ROUTE_ROWS_PACKED = 3,  /* packed into the lane's pinned staging buffer, one copy per run of such alignments */
+    MSA_ROUTE_ROWS_FETCHED = 4  /* small page-locked rows read by fetch_rows_batch_kernel */
+};
+int msa_batch_debug_routes(msa_batch *b, int32_t *route, int32_t cap);
 /* 1 when the library honours its MSA_* diagnostic switches in this process: the build has them (not -DMSA_NO_DIAGNOSTICS) and
  * the environment variable MSA_DIAGNOSTICS is set.  Without it every context and batch object takes the default dispatch
  * whatever else the environment holds (MSA_TRACE, which only prints, is always read).  Needs no device. */

@@ -46,7 +46,7 @@ EXPORTS = [
     "msa_gaps_cutpoint_2nd_slope", "msa_similarity_cutpoint", "msa_clean_gaps",
     "msa_clean_similarity", "msa_clean_both", "msa_clean_strict", "msa_select_method",
     "msa_representatives", "msa_cutpoint_clusters", "msa_trim", "msa_trim_only_gaps_rows", "msa_batch_create", "msa_batch_destroy", "msa_batch_workers", "msa_trim_batch",
-    "msa_batch_only_gaps_rows", "msa_batch_last_hip_error", "msa_prof_get", "msa_prof_reset",
+    "msa_batch_only_gaps_rows", "msa_batch_last_hip_error", "msa_batch_debug_routes", "msa_prof_get", "msa_prof_reset",
     "msa_prof_enable", "msa_debug_sim_launches", "msa_debug_last_paths", "msa_debug_switches_enabled", "msa_fasta_scan", "msa_fasta_fill", "msa_clustal_scan", "msa_clustal_fill",
     "msa_upload_fasta", "msa_text_names", "msa_download_rows", "msa_trim_batch_fasta", "msa_batch_fasta_result",
     "msa_text_size", "msa_emit_text", "msa_download_text", "msa_trim_batch_fasta_emit", "msa_batch_fasta_text",
@@ -201,6 +201,7 @@ def load():
         L.msa_trim_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.msa_batch_only_gaps_rows.argtypes = [vp, i32, vp, i32]
         L.msa_batch_last_hip_error.argtypes = [vp, i32]
+        L.msa_batch_debug_routes.argtypes = [vp, vp, i32]
         L.msa_batch_last_hip_error.restype = ctypes.c_char_p
         L.msa_upload_fasta.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.POINTER(TextInfo), ctypes.POINTER(ErrDetail)]
         L.msa_text_names.argtypes = [vp, vp, vp]
@@ -778,6 +779,28 @@ class Batch:
                     rec.text = ctypes.string_at(p_text.value, t_len.value) if t_len.value > 0 else (b"" if t_len.value == 0 else None)
                     rec.text_flags = int(t_flags.value)
                 out.append(rec)
+        return out
+
+    ROUTE_ROWS = ("none", "linear", "copy_2d", "packed", "fetched")
+
+    def last_routes(self):
+        """Which way every alignment of the last `trim` went (`msa_batch_debug_routes`; diagnostics, tests/test_gpu_batch_engine.py):
+        per alignment a dict -- `engine` (False: a worker context took it, and the other entries say nothing), `group` (its index
+        in the call), `lane_per_column` and `several_launches` (how the group ran its similarity statistic), `rows` (how they
+        went up: "linear", "copy_2d", "packed" or "fetched"), `redone` (the selection fell back to an ordinary context)."""
+        with self._lock:
+            if not self.h:
+                raise BatchClosed("the batch object is closed")
+            count = self.lib.msa_batch_debug_routes(self.h, None, 0)
+            if count < 0:
+                raise MsaError(count, self.lib.msa_strerror(count).decode())
+            raw = np.zeros(max(count, 1), dtype=np.int32)
+            self.lib.msa_batch_debug_routes(self.h, ptr(raw), count)
+        out = []
+        for v in raw[:count].tolist():
+            rows = (v >> 4) & 7
+            out.append(dict(engine=bool(v & 1), group=v >> 8 if v & 1 else -1, lane_per_column=bool(v & 2), several_launches=bool(v & 4),
+                            redone=bool(v & 8), rows=self.ROUTE_ROWS[rows] if rows < len(self.ROUTE_ROWS) else rows))
         return out
 
     def check(self, rc, info):

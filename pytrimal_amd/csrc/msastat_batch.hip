@@ -79,6 +79,7 @@ struct msa_batch {
         uint32_t text_flags = 0;          // MSA_TEXT_F_*
     };
     std::vector<FastaResult> fasta;  // per text of the last TEXTS call (none after a ROWS call)
+    std::vector<int32_t> routes;     // per alignment of the last ROWS call: MSA_ROUTE_* (msa_batch_debug_routes; none after a TEXTS call)
 };
 
 // ---- the batch engine: one launch per kernel family for a whole group of alignments -------------------------------------
@@ -530,7 +531,7 @@ static int engine_launch(const BatchCall &c, msa_ctx *tc, Engine::Lane &L, const
 }
 
 // one group on lane L: layout, tables, uploads, launches; engine_finish waits for it
-int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<Engine::Item> &group) {
+int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<Engine::Item> &group, int group_index) {
     const BatchCall &c = b->call;
     msa_ctx *tc = e->tables;
     const int K = (int)group.size();
@@ -545,6 +546,17 @@ int engine_enqueue(msa_batch *b, Engine *e, Engine::Lane &L, const std::vector<E
     L.items = group;
     EngineGroup g = engine_layout(c, e, L.items);
     engine_row_routes(c, e, L.items, g);
+    for (int i = 0; i < K; ++i) {  // what was decided, for msa_batch_debug_routes
+        const int k = L.items[i].k;
+        const bool sim = L.items[i].kind == ENGINE_SIMILARITY;
+        const int rows = g.fetch[i] ? MSA_ROUTE_ROWS_FETCHED
+                         : g.packed[i] ? MSA_ROUTE_ROWS_PACKED
+                         : c.ld[k] == (int64_t)round_up(c.n[k], 64) ? MSA_ROUTE_ROWS_LINEAR
+                                                                    : MSA_ROUTE_ROWS_COPY_2D;
+        b->routes[k] = MSA_ROUTE_ENGINE | (sim && g.cols_mode ? MSA_ROUTE_LANE_PER_COLUMN : 0) |
+                       (sim && !g.cols_mode && g.multi ? MSA_ROUTE_SEVERAL_LAUNCHES : 0) | rows << MSA_ROUTE_ROWS_SHIFT |
+                       group_index << MSA_ROUTE_GROUP_SHIFT;
+    }
     HIPCHK(tc, L.arena.reserve(g.arena_bytes));
     g.mix((uint64_t)(uintptr_t)L.arena.p);
     const size_t meta_bytes = engine_meta_bytes(K);
@@ -620,6 +632,7 @@ void engine_select_item(msa_batch *b, Engine::Lane &L, const Engine::Item &it, m
         if (v->tuning.trace) std::fprintf(stderr, "[engine] alignment %d (%d x %d) needs the device again: ordinary context\n", k, m, n);
         std::lock_guard<std::mutex> lk(b->mu);
         b->sel_redo.push_back(k);
+        b->routes[k] |= MSA_ROUTE_SELECTION_REDONE;
         return;
     }
     b->only_gaps[k] = v->only_gaps_rows;
@@ -768,7 +781,7 @@ int engine_run(msa_batch *b, const std::vector<Engine::Item> &share) {
         Engine::Lane &L = e->lanes[g % e->nlanes];
         rc = engine_finish(b, e, L);  // (the group that used this lane `nlanes` steps ago)
         const auto te = std::chrono::steady_clock::now();
-        if (rc == MSA_OK) rc = engine_enqueue(b, e, L, groups[g]);
+        if (rc == MSA_OK) rc = engine_enqueue(b, e, L, groups[g], g);
         if (e->trace)
             std::fprintf(stderr, "[engine] group %d enqueued in %.0f us\n", g,
                          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - te).count());
@@ -937,6 +950,7 @@ static int run_call(msa_batch *b, const BatchCall &call, Key key) {
         b->only_gaps.assign(count, {});
         b->fasta.clear();
         if (!rows) b->fasta.resize((size_t)count);
+        b->routes.assign(rows ? (size_t)count : 0, 0);
         for (int32_t k = 0; k < count; ++k) call.rc[k] = MSA_OK;
         b->next.store(0);
         b->running = b->order.empty() ? 0 : (int)b->workers.size();
@@ -1069,6 +1083,14 @@ int msa_batch_only_gaps_rows(msa_batch *b, int32_t k, int32_t *rows, int32_t cap
     const std::vector<int32_t> &v = b->only_gaps[k];
     std::copy_n(v.begin(), std::min((int)v.size(), (int)cap), rows);
     return (int)v.size();
+}
+
+int msa_batch_debug_routes(msa_batch *b, int32_t *route, int32_t cap) {
+    if (!b || cap < 0 || (!route && cap > 0)) return MSA_E_INVALID;
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (b->in_call) return MSA_E_INVALID;
+    std::copy_n(b->routes.begin(), std::min((int)b->routes.size(), (int)cap), route);
+    return (int)b->routes.size();
 }
 
 const char *msa_batch_last_hip_error(const msa_batch *b, int32_t worker) {

@@ -242,6 +242,7 @@ int main(void) {
     if (strcmp(msa_strerror(MSA_E_WINDOW_TOO_BIG), "window size is too big for this alignment") != 0) return 4;
     if (msa_trim(NULL, &p, keep, keep, &info) != MSA_E_INVALID) return 5;           /* argument checks need no device */
     if (msa_trim_batch(NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) != MSA_E_INVALID) return 6;
+    if (msa_batch_debug_routes(NULL, w, 8) != MSA_E_INVALID) return 7;
     printf("%d %d %d %d %d %d %d %d | %d%d%d%d%d%d%d%d\n", w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], keep[0], keep[1], keep[2],
            keep[3], keep[4], keep[5], keep[6], keep[7]);
     return 0;
