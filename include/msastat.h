@@ -189,18 +189,35 @@ int msa_download_rows(msa_ctx *ctx, uint8_t *rows, int64_t ld);
 
 /* ---- trimmed alignment text composed on the device: what `Alignment.dump` / `dumps` (reference _trimal.pyx:604-731) get
  *      from trimAl's FormatManager (format_handling.pxd:11-32) for the kept sequences and residues, without host rows.
- *      The bytes are those of pytrimal_amd's host writers (alignment.py: _fast_fasta, _fast_clustal), corner cases included. --- */
+ *      The bytes are those of pytrimal_amd's host writers (alignment.py: _fast_fasta, _fast_clustal, _write_phylip40,
+ *      _write_phylip32, _write_phylippaml), corner cases included. --- */
 enum {
     MSA_TEXT_FASTA = 0,     /* per kept sequence ">name\n", then its kept residues in lines of 60 */
     MSA_TEXT_FASTA_M10 = 1, /* the same with every name cut to its first 10 bytes ("fasta_m10") */
-    MSA_TEXT_CLUSTAL = 2    /* header line, empty line, blocks of 60 kept columns: name padded to the longest kept name + 5 */
+    MSA_TEXT_CLUSTAL = 2,   /* header line, empty line, blocks of 60 kept columns: name padded to the longest kept name + 5 */
+    /* The PHYLIP family (alignment.py: _write_phylip40, _write_phylip32, _write_phylippaml), a second range of codes.  With km
+     * kept sequences, kn kept columns, L_i the bytes of kept name i that reach the text (cut to 10 for _M10):
+     * W = max(max L_i, 10) + 3, g(c) = c + ceil(c / 10) - 1 (c residues in groups of ten joined by one blank; g(0) = 0),
+     * nb = max(ceil(kn / 60), 1) blocks of c_b = min(60, kn - 60 b) columns, H the bytes of the header " km kn\n" (kn printed
+     * as 0 when km is 0).  kn == 0 gives one block of name-only lines; km == 0 gives " 0 0\n\n" (PHYLIP40) or " 0 0\n". */
+    MSA_TEXT_PHYLIP40 = 16,       /* interleaved ("phylip", "phylip40"): H, then per block b km lines of W + g(c_b) + 1 bytes -- the
+                                     name (block 0) or nothing, blanks up to W, the grouped residues, '\n' -- and one '\n':
+                                     H + sum_b (km (W + g(c_b) + 1) + 1) bytes */
+    MSA_TEXT_PHYLIP40_M10 = 17,
+    MSA_TEXT_PHYLIP32 = 18,       /* sequential: H, then per sequence its nb lines (the name on the first only) and one '\n': records
+                                     of S = sum_b (W + g(c_b) + 1) + 1 bytes, record i at H + i S, H + km S bytes */
+    MSA_TEXT_PHYLIP32_M10 = 19,
+    MSA_TEXT_PHYLIPPAML = 20,     /* H, then per sequence one line of W + kn + 1 bytes: the name, blanks up to W, all residues
+                                     ungrouped, '\n': H + km (W + kn + 1) bytes */
+    MSA_TEXT_PHYLIPPAML_M10 = 21
 };
 enum {
-    MSA_TEXT_F_NON_ASCII = 1u << 0, /* a kept name holds a byte >= 0x80: no text (the host writer counts characters there) */
+    MSA_TEXT_F_NON_ASCII = 1u << 0, /* a kept name holds a byte >= 0x80: no text (the host writer counts characters there: the
+                                       padding of Clustal and PHYLIP, the cut to 10) */
     MSA_TEXT_F_TOO_LONG = 1u << 1   /* the text would have 2^31 bytes or more: no text (the call returns MSA_E_INVALID) */
 };
 /* The length of that text from the closed form (replaces nothing in the reference, whose writer streams: it is what sizes
- * the buffers): kept_m sequences with names of name_len[i] bytes (cut to 10 here for MSA_TEXT_FASTA_M10) and kept_n
+ * the buffers): kept_m sequences with names of name_len[i] bytes (cut to 10 here for the _M10 formats) and kept_n
  * residues each.  Pure host function: needs no device.  MSA_E_INVALID for an unknown format or a negative count. */
 int msa_text_size(int32_t format, int32_t kept_m, int32_t kept_n, const int32_t *name_len, int64_t *out);
 /* Composes, on the context's stream, the text of the context's current alignment under keep_res[n] / keep_seq[m] (host

@@ -103,7 +103,9 @@ W_ONLY_GAPS_SEQUENCES, W_NO_COLUMNS_LEFT, W_UNDEFINED_IDENTITY = 1, 2, 4
 FASTA_MAX_BYTES = (1 << 31) - 1
 
 # the formats msa_emit_text composes on the device (MSA_TEXT_*), by the name `Alignment.dumps` knows them under
-TEXT_FORMATS = {"fasta": 0, "fasta_m10": 1, "clustal": 2}
+# ("phylip" is `dumps`' alias of "phylip40": whoever routes a `dumps` name here resolves it first, as `trim_files` does)
+TEXT_FORMATS = {"fasta": 0, "fasta_m10": 1, "clustal": 2, "phylip40": 16, "phylip40_m10": 17, "phylip32": 18, "phylip32_m10": 19,
+                "phylippaml": 20, "phylippaml_m10": 21}
 TEXT_F_NON_ASCII, TEXT_F_TOO_LONG = 1, 2
 
 
@@ -458,8 +460,8 @@ class Context:
     def emit_text(self, format, keep_res=None, keep_seq=None, names=None):
         """The text `TrimmedAlignment.dumps(format)` gives for this context's alignment under the masks `keep_res` [n] /
         `keep_seq` [m] (None: keep all), composed on the device (`msa_emit_text` + `msa_download_text`), as bytes.  `format`:
-        "fasta", "fasta_m10" or "clustal".  `names`: the m sequences' names (bytes each); None: the names in the text of the
-        last `upload_fasta`.  Returns None when a kept name holds a non-ASCII byte: the host writer counts characters
+        a name of `TEXT_FORMATS` ("fasta", "clustal", "phylip40", "phylip32", "phylippaml", ...).  `names`: the m sequences'
+        names (bytes each); None: the names in the text of the last `upload_fasta`.  Returns None when a kept name holds a non-ASCII byte: the host writer counts characters
         there, and is the one to use.  A text of 2^31 bytes or more raises `MsaError` (E_INVALID)."""
         code = text_format_code(format)
         m, n = self.shape
@@ -734,8 +736,8 @@ class Batch:
 
     def trim_fasta(self, texts, valid, params3, want_rows=False, emit=None):
         """`texts`: FASTA texts (bytes-like, each < 2^31 bytes), `params3`: `TrimParams * 3` by type (msa_trim_batch_fasta)
-        -> per text a `TrimRecord` (what `trim_files` adds left empty; `rows` with `want_rows`).  `emit`: "fasta", "fasta_m10"
-        or "clustal" -- the workers also compose the trimmed text on the device (msa_trim_batch_fasta_emit): `text` and
+        -> per text a `TrimRecord` (what `trim_files` adds left empty; `rows` with `want_rows`).  `emit`: a name
+        of `TEXT_FORMATS` -- the workers also compose the trimmed text on the device (msa_trim_batch_fasta_emit): `text` and
         `text_flags`.  The interpreter lock is released for the whole call."""
         emit_code = None if emit is None else text_format_code(emit)
         count = len(texts)

@@ -295,11 +295,12 @@ def trim_files(trimmer, files, matrix=None, *, format=None, masks_only=False, th
     `output`: a sequence as long as `files` of paths or binary file objects.  The call then also writes, for every file,
     the bytes ``result.dump(output[k], output_format)`` writes for the `TrimmedAlignment` it returns (or would return
     without `masks_only`), and returns what it returns without `output`.  For FASTA inputs and `output_format` "fasta",
-    "fasta_m10" or "clustal" the native workers compose the text on the device behind the trim, under the masks it
-    produced and with the names in the input text (`msa_trim_batch_fasta_emit`), and only the text comes back: with
-    `masks_only=True` no rows are downloaded -- files in, files out.  Everything else (inputs that went through
-    `Alignment.load`, a name with a non-ASCII byte, the other formats, a text of 2^31 bytes or more) is written by the
-    host writer from host rows, the same bytes.  A wrong length of `output` and a format `dumps` does not know are
+    "fasta_m10", "clustal", "phylip" / "phylip40", "phylip32", "phylippaml" or one of the three PHYLIP formats' "_m10"
+    variants the native workers compose the text on the device behind the trim, under the masks it produced and with
+    the names in the input text (`msa_trim_batch_fasta_emit`), and only the text comes back: with `masks_only=True` no
+    rows are downloaded -- files in, files out.  Everything else (inputs that went through `Alignment.load`, a name with
+    a non-ASCII byte, the other formats -- NEXUS, MEGA, PIR / NBRF, HTML --, a text of 2^31 bytes or more) is written by
+    the host writer from host rows, the same bytes.  A wrong length of `output` and a format `dumps` does not know are
     `ValueError`s before any work; nothing is written unless every file loaded and every trim succeeded, and the outputs
     are then written in input order.
     """
@@ -374,7 +375,8 @@ def _check_output(output, output_format, count):
     base = fmt_out[:-4] if short else fmt_out
     if base not in _WRITERS or (short and base not in _M10_FORMATS):
         raise ValueError(f"Could not recognize alignment format: {output_format!r}")
-    return output, (fmt_out if fmt_out in _lib.TEXT_FORMATS else None)
+    emit = ("phylip40" + fmt_out[6:]) if base == "phylip" else fmt_out  # (`dumps`' alias, which the device table does not hold)
+    return output, (emit if emit in _lib.TEXT_FORMATS else None)
 
 
 def _read_texts(files, format):

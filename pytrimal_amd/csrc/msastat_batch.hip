@@ -1049,7 +1049,7 @@ int msa_trim_batch_fasta(msa_batch *b, int32_t count, const uint8_t *const *text
 
 int msa_trim_batch_fasta_emit(msa_batch *b, int32_t count, const uint8_t *const *texts, const int64_t *lens, const uint8_t *valid,
                               const msa_trim_params params_by_type[3], int32_t want_rows, int32_t format, int32_t *rc) {
-    if (format < MSA_TEXT_FASTA || format > MSA_TEXT_CLUSTAL) return MSA_E_INVALID;
+    if (!msai::text_format_known(format)) return MSA_E_INVALID;
     return trim_batch_fasta(b, count, texts, lens, valid, params_by_type, want_rows, format, rc);
 }
 

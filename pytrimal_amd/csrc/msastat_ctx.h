@@ -88,6 +88,9 @@ struct ProfEntry {
 
 inline int round_up(int x, int q) { return (x + q - 1) / q * q; }
 
+// a MSA_TEXT_* code the device writer composes (the two ranges of include/msastat.h)
+inline bool text_format_known(int f) { return (f >= MSA_TEXT_FASTA && f <= MSA_TEXT_CLUSTAL) || (f >= MSA_TEXT_PHYLIP40 && f <= MSA_TEXT_PHYLIPPAML_M10); }
+
 }  // namespace msai
 using msai::DevBuf;
 using msai::DevView;

@@ -1,20 +1,26 @@
 // msastat_emit.hip -- the context's residue matrix + masks + names -> the text of the trimmed alignment in device memory
 // (msa_text_size, msa_emit_text, msa_download_text of include/msastat.h): the bytes pytrimal_amd's host writers produce
-// (alignment.py: _fast_fasta, _fast_clustal), without host rows.
+// (alignment.py: _fast_fasta, _fast_clustal, _write_phylip40, _write_phylip32, _write_phylippaml), without host rows.
 //
-// Both layouts are closed forms of the kept counts and the kept names' lengths.  With km kept sequences, kn kept columns,
+// All layouts are closed forms of the kept counts and the kept names' lengths.  With km kept sequences, kn kept columns,
 // L_i the bytes of kept name i that reach the text and R = kn + ceil(kn / 60) (a record's residues and line ends):
 //   FASTA    record i starts at P_i + i * R with P_i = sum_{j<i} (2 + L_j); it is '>' name '\n', then R bytes in which every 61st
 //            (and the last) is '\n';
 //   Clustal  37 header bytes, then blocks of B = km * (W + 61) + 2 bytes (the last one shorter), W = max L_i + 5: km lines of
 //            name, blanks up to W, the block's residues, '\n', and two '\n' behind them.
+// The PHYLIP family: H header bytes " km kn\n", W = max(max L_i, 10) + 3, nb = max(ceil(kn / 60), 1) blocks of c_b = min(60,
+// kn - 60 b) columns, a line's residues in groups of ten joined by one blank: g(c) = c + ceil(c / 10) - 1 bytes (g(0) = 0);
+//   PHYLIP40    per block km lines of W + g(c_b) + 1 bytes (the name in block 0 only, blanks up to W, the groups, '\n'), then '\n';
+//   PHYLIP32    per sequence its nb lines, then '\n': records of S = sum_b (W + g(c_b) + 1) + 1 bytes, record i at H + i * S;
+//   PHYLIPPAML  per sequence one line of W + kn + 1 bytes: the name, blanks up to W, all residues ungrouped, '\n'.
 // Two passes, none of which waits for another workgroup:
 //   emit_index_kernel     one workgroup: exclusive scans of the two masks -> the kept-column and kept-row lists; over the kept
 //                         rows a scan of 2 + L_i -> P_i, the longest name, and whether a kept name holds a byte >= 0x80 (the
 //                         host writer counts characters there, the caller takes it instead);
 //   emit_fasta_kernel /   output-driven: a lane owns 16 consecutive bytes of the text, finds its record (a binary search over
-//   emit_clustal_kernel   the record starts) or block and line (two divisions) once, then walks: every byte is '>' / ' ' /
-//                         '\n', a name byte, or raw[row * ld + col[k]]; one aligned 16-byte store per lane, no atomics.
+//   emit_clustal_kernel / the record starts) or block and line (two divisions; PHYLIP's records are uniform) once, then walks:
+//   emit_phylip_kernel    every byte is '>' / ' ' / '\n', a header or name byte, or raw[row * ld + col[k]]; one aligned
+//                         16-byte store per lane, no atomics.
 // Work per byte does not depend on the line length or on how many columns the masks dropped.  Positions in the text are 32-bit
 // (a text of 2^31 bytes or more is refused before the second pass), offsets into the matrix 64-bit.
 #include "msastat_ctx.h"
@@ -28,6 +34,10 @@ constexpr int LINE = 60;        // residues per line, both formats
 constexpr int CLUSTAL_HEAD = 37;
 __device__ const char CLUSTAL_HEAD_TEXT[CLUSTAL_HEAD + 1] = "CLUSTAL multiple sequence alignment\n\n";
 constexpr int FASTA_M10 = 10;
+constexpr int GROUP = 10;       // PHYLIP: residues per group
+constexpr int PHYLIP_HEAD = 24; // the longest header, " 2147483647 2147483647\n", fits
+constexpr int PHYLIP_MINW = 10, PHYLIP_PAD = 3;
+enum { P40 = 0, P32 = 1, PAML = 2 };  // the PHYLIP layouts
 
 enum { ES_KM = 0, ES_KN = 1, ES_NAMES = 2 /* sum of 2 + L_i */, ES_MAXL = 3, ES_FLAG = 4, ES_WORDS = 8 };
 
@@ -54,6 +64,12 @@ struct ComposeArgs {
     int width;        // Clustal: the name column
     uint32_t total;   // bytes of the text (< 2^31)
     uint8_t *out;     // writable up to the next multiple of 16
+};
+
+struct PhylipArgs {
+    ComposeArgs c;                // width: W
+    uint8_t head[PHYLIP_HEAD];    // the header line, formatted on the host
+    int hlen;
 };
 
 // exclusive scan of one value per thread over the workgroup; *total = the sum (sh: ET words)
@@ -231,10 +247,117 @@ __global__ __launch_bounds__(CT) void emit_clustal_kernel(ComposeArgs a) {
     *reinterpret_cast<uint4 *>(a.out + pos0) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// the text's length from the kept counts, sum (2 + L_i) and max L_i (saturates at INT64_MAX)
+// bytes of a PHYLIP line's residue part: c residues in groups of ten joined by one blank
+__host__ __device__ __forceinline__ uint32_t grouped(uint32_t c) { return c ? c + (c + GROUP - 1) / GROUP - 1 : 0; }
+
+template <int LAYOUT>
+__global__ __launch_bounds__(CT) void emit_phylip_kernel(PhylipArgs pa) {
+    const ComposeArgs &a = pa.c;
+    const uint32_t pos0 = (blockIdx.x * (uint32_t)CT + threadIdx.x) * (uint32_t)EB;
+    if (pos0 >= a.total) return;
+    const uint32_t km = (uint32_t)a.km, kn = (uint32_t)a.kn, W = (uint32_t)a.width, H = (uint32_t)pa.hlen;
+    const uint32_t nb = LAYOUT == PAML ? 1u : max((kn + LINE - 1) / LINE, 1u);
+    const uint32_t LF = W + grouped(LINE) + 1;  // a line of a full block
+    // columns of block b (0 behind the last one, where nothing is read) and the bytes of its lines
+    auto columns = [&](uint32_t b) { return LAYOUT == PAML ? kn : (LINE * b < kn ? min((uint32_t)LINE, kn - LINE * b) : 0u); };
+    auto line_bytes = [&](uint32_t c) { return W + (LAYOUT == PAML ? c : grouped(c)) + 1; };
+    // the walk's state behind the header: block b, sequence i, byte j of its line of Lb bytes; term: the '\n' behind a block
+    // (P40) or behind a sequence's lines (P32) comes next
+    uint32_t b = 0, i = 0, j = 0, Lb = 0, cur = 0xffffffffu, L = 0;
+    bool term = false, placed = false;
+    const uint8_t *name = nullptr, *src = nullptr;
+    uint32_t w[4] = {0, 0, 0, 0};
+    const int cnt = (int)min((uint32_t)EB, a.total - pos0);
+#pragma unroll
+    for (int x = 0; x < EB; ++x) {
+        if (x >= cnt) continue;
+        const uint32_t p = pos0 + x;
+        if (p < H) {
+            put(w, x, (uint32_t)pa.head[p]);
+            continue;
+        }
+        if (!placed) {  // (every divisor is a part of the text that exists, so it is below 2^31; km == 0: P40's one '\n')
+            const uint32_t q = p - H;
+            if (LAYOUT == P40) {
+                b = nb > 1 ? min(q / (km * LF + 1), nb - 1) : 0u;
+                const uint32_t off = q - b * (km * LF + 1);
+                Lb = line_bytes(columns(b));
+                if (off >= km * Lb) term = true;
+                else i = off / Lb, j = off - i * Lb;
+            } else if (LAYOUT == P32) {
+                const uint32_t S = (nb - 1) * LF + line_bytes(columns(nb - 1)) + 1;
+                i = q / S;
+                const uint32_t off = q - i * S;
+                if (off == S - 1) term = true;
+                else b = min(off / LF, nb - 1), j = off - b * LF;
+                Lb = line_bytes(columns(b));
+            } else {
+                Lb = line_bytes(kn);
+                i = q / Lb, j = q - i * Lb;
+            }
+            placed = true;
+        }
+        uint32_t c;
+        if (term) {
+            c = '\n';
+            term = false, j = 0;
+            if (LAYOUT == P40) ++b, i = 0;
+            else ++i, b = 0;
+            Lb = line_bytes(columns(b));
+        } else {
+            if (i != cur) {
+                cur = i;
+                L = (uint32_t)a.nlenk[i];
+                const int row = a.rows[i];
+                name = a.nbase + a.noff[row];
+                src = a.raw + (size_t)row * (size_t)a.ld;
+            }
+            if (j < W) c = (b == 0 && j < L) ? (uint32_t)name[j] : (uint32_t)' ';
+            else if (j == Lb - 1) c = '\n';
+            else if (LAYOUT == PAML) c = src[a.cols[j - W]];
+            else {
+                const uint32_t r = j - W, grp = r / (GROUP + 1), at = r - grp * (GROUP + 1);
+                c = at == GROUP ? (uint32_t)' ' : (uint32_t)src[a.cols[b * LINE + grp * GROUP + at]];
+            }
+            if (++j == Lb) {
+                j = 0;
+                if (LAYOUT == P40) term = ++i == km;
+                else if (LAYOUT == P32) term = ++b == nb, Lb = line_bytes(columns(b));
+                else ++i;
+            }
+        }
+        put(w, x, c);
+    }
+    *reinterpret_cast<uint4 *>(a.out + pos0) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+bool is_m10(int format) {
+    return format == MSA_TEXT_FASTA_M10 || format == MSA_TEXT_PHYLIP40_M10 || format == MSA_TEXT_PHYLIP32_M10 || format == MSA_TEXT_PHYLIPPAML_M10;
+}
+bool is_phylip(int format) { return format >= MSA_TEXT_PHYLIP40 && format <= MSA_TEXT_PHYLIPPAML_M10; }
+int phylip_layout(int format) { return (format - MSA_TEXT_PHYLIP40) / 2; }
+
+// PHYLIP's header line " km kn\n" (kn printed as 0 without sequences, as the host writer does) -> its length
+int phylip_head(char (&out)[PHYLIP_HEAD + 1], int64_t km, int64_t kn) {
+    return std::snprintf(out, sizeof out, " %lld %lld\n", (long long)km, (long long)(km ? kn : 0));
+}
+
+// the text's length from the kept counts, sum (2 + L_i) and max L_i, both with the cut to 10 applied (saturates at INT64_MAX)
 int64_t text_total(int format, int64_t km, int64_t kn, int64_t names_bytes, int64_t max_len) {
     unsigned __int128 t;
-    if (format == MSA_TEXT_CLUSTAL) {
+    if (is_phylip(format)) {
+        using u128 = unsigned __int128;
+        char head[PHYLIP_HEAD + 1];
+        if (km == 0) kn = 0;
+        const u128 H = (u128)phylip_head(head, km, kn), W = (u128)std::max<int64_t>(max_len, PHYLIP_MINW) + PHYLIP_PAD;
+        const int64_t full = kn / LINE, rest = kn % LINE, nb = std::max<int64_t>(full + (rest != 0), 1);
+        // a sequence's lines over all blocks: nb names or paddings and line ends, the residues, their blanks
+        const u128 lines = (u128)nb * (W + 1) + (u128)kn + (u128)full * (grouped(LINE) - LINE) + (u128)(grouped((uint32_t)rest) - (uint32_t)rest);
+        const int layout = phylip_layout(format);
+        if (layout == P40) t = H + (u128)km * lines + (u128)nb;
+        else if (layout == P32) t = H + (u128)km * (lines + 1);
+        else t = H + (u128)km * (W + (u128)kn + 1);
+    } else if (format == MSA_TEXT_CLUSTAL) {
         if (km == 0 || kn == 0) return CLUSTAL_HEAD;
         const unsigned __int128 nb = (unsigned __int128)((kn + LINE - 1) / LINE);
         t = (unsigned __int128)CLUSTAL_HEAD + nb * 2 + (unsigned __int128)km * (nb * (unsigned __int128)(max_len + 5 + 1) + (unsigned __int128)kn);
@@ -253,13 +376,12 @@ using namespace msai;
 extern "C" {
 
 int msa_text_size(int32_t format, int32_t kept_m, int32_t kept_n, const int32_t *name_len, int64_t *out) {
-    if (!out || format < MSA_TEXT_FASTA || format > MSA_TEXT_CLUSTAL || kept_m < 0 || kept_n < 0 || (kept_m > 0 && !name_len))
-        return MSA_E_INVALID;
+    if (!out || !text_format_known(format) || kept_m < 0 || kept_n < 0 || (kept_m > 0 && !name_len)) return MSA_E_INVALID;
     int64_t bytes = 0, mx = 0;
     for (int32_t i = 0; i < kept_m; ++i) {
         if (name_len[i] < 0) return MSA_E_INVALID;
-        const int64_t L = name_len[i];
-        bytes += 2 + (format == MSA_TEXT_FASTA_M10 ? std::min<int64_t>(L, FASTA_M10) : L);
+        const int64_t L = is_m10(format) ? std::min<int64_t>(name_len[i], FASTA_M10) : name_len[i];
+        bytes += 2 + L;
         mx = std::max(mx, L);
     }
     *out = text_total(format, kept_m, kept_n, bytes, mx);
@@ -268,7 +390,7 @@ int msa_text_size(int32_t format, int32_t kept_m, int32_t kept_n, const int32_t 
 
 int msa_emit_text(msa_ctx *c, int32_t format, const uint8_t *keep_res, const uint8_t *keep_seq, const uint8_t *names,
                   const int64_t *name_off, const int32_t *name_len, int64_t *len_out, uint32_t *flags_out) {
-    if (!c || !len_out || format < MSA_TEXT_FASTA || format > MSA_TEXT_CLUSTAL) return MSA_E_INVALID;
+    if (!c || !len_out || !text_format_known(format)) return MSA_E_INVALID;
     *len_out = 0;
     if (flags_out) *flags_out = 0;
     c->em_len = -1;
@@ -321,7 +443,7 @@ int msa_emit_text(msa_ctx *c, int32_t format, const uint8_t *keep_res, const uin
     } else {
         ia.nbase = c->fa_text.p, ia.noff = c->fa_names.p, ia.nend = c->fa_names.p + m, ia.nlen = nullptr;
     }
-    ia.cap = format == MSA_TEXT_FASTA_M10 ? FASTA_M10 : INT32_MAX;
+    ia.cap = is_m10(format) ? FASTA_M10 : INT32_MAX;
     ia.pre = reinterpret_cast<long long *>(x), ia.stats = reinterpret_cast<long long *>(x + i_stats);
     ia.cols = reinterpret_cast<int32_t *>(x + i_cols), ia.rows = reinterpret_cast<int32_t *>(x + i_rows);
     ia.nlenk = reinterpret_cast<int32_t *>(x + i_nlen);
@@ -335,7 +457,8 @@ int msa_emit_text(msa_ctx *c, int32_t format, const uint8_t *keep_res, const uin
         if (flags_out) *flags_out |= MSA_TEXT_F_NON_ASCII;
         return MSA_OK;
     }
-    const int64_t total = text_total(format, km, kn, st[ES_NAMES], st[ES_MAXL]);
+    const int64_t max_len = std::min<int64_t>(st[ES_MAXL], ia.cap);  // (the index pass takes the longest name before the cut)
+    const int64_t total = text_total(format, km, kn, st[ES_NAMES], max_len);
     if (total > (int64_t)INT32_MAX) {
         if (flags_out) *flags_out |= MSA_TEXT_F_TOO_LONG;
         return MSA_E_INVALID;
@@ -344,9 +467,19 @@ int msa_emit_text(msa_ctx *c, int32_t format, const uint8_t *keep_res, const uin
         HIPCHK(c, c->em_out.reserve(up16((size_t)total) + 64));
         ComposeArgs ca;
         ca.raw = c->raw, ca.ld = c->ld, ca.nbase = ia.nbase, ca.noff = ia.noff, ca.pre = ia.pre, ca.cols = ia.cols, ca.rows = ia.rows;
-        ca.nlenk = ia.nlenk, ca.km = (int)km, ca.kn = (int)kn, ca.width = (int)st[ES_MAXL] + 5, ca.total = (uint32_t)total, ca.out = c->em_out.p;
+        ca.nlenk = ia.nlenk, ca.km = (int)km, ca.kn = (int)kn, ca.width = (int)max_len + 5, ca.total = (uint32_t)total, ca.out = c->em_out.p;
         const unsigned grid = (unsigned)(((size_t)total + (size_t)CT * EB - 1) / ((size_t)CT * EB));
-        if (format == MSA_TEXT_CLUSTAL) emit_clustal_kernel<<<grid, CT, 0, c->stream>>>(ca);
+        if (is_phylip(format)) {
+            PhylipArgs pa;
+            char head[PHYLIP_HEAD + 1] = {};
+            pa.c = ca, pa.c.kn = km ? (int)kn : 0, pa.c.width = (int)std::max<int64_t>(max_len, PHYLIP_MINW) + PHYLIP_PAD;
+            pa.hlen = phylip_head(head, km, kn);
+            std::memcpy(pa.head, head, PHYLIP_HEAD);
+            const int layout = phylip_layout(format);
+            if (layout == P40) emit_phylip_kernel<P40><<<grid, CT, 0, c->stream>>>(pa);
+            else if (layout == P32) emit_phylip_kernel<P32><<<grid, CT, 0, c->stream>>>(pa);
+            else emit_phylip_kernel<PAML><<<grid, CT, 0, c->stream>>>(pa);
+        } else if (format == MSA_TEXT_CLUSTAL) emit_clustal_kernel<<<grid, CT, 0, c->stream>>>(ca);
         else emit_fasta_kernel<<<grid, CT, 0, c->stream>>>(ca);
         HIPCHK(c, hipGetLastError());
         if (std::getenv("MSA_TRACE"))
