@@ -554,15 +554,20 @@ class Context:
         check(self.lib, self.h, self.lib.msa_overlap(self.h, residue_overlap, ptr(out)))
         return out
 
-    def trim(self, params):
+    def trim_rc(self, params):
+        """`msa_trim` with nothing raised: (keep_res, keep_seq, TrimInfo, return code) -- a failure's detail is `info.err`"""
         m, n = self.shape
         keep_res = np.ones(n, dtype=np.uint8)
         keep_seq = np.ones(m, dtype=np.uint8)
         info = TrimInfo()
         rc = self.lib.msa_trim(self.h, ctypes.byref(params), ptr(keep_res), ptr(keep_seq), ctypes.byref(info))
         self._in_flight = None  # (msa_trim waited for the stream, error or not)
+        return keep_res.astype(bool), keep_seq.astype(bool), info, rc
+
+    def trim(self, params):
+        keep_res, keep_seq, info, rc = self.trim_rc(params)
         check(self.lib, self.h, rc, info.err)
-        return keep_res.astype(bool), keep_seq.astype(bool), info
+        return keep_res, keep_seq, info
 
     def only_gaps_rows(self):
         """The sequences the last `trim` removed because it left them with gaps only."""

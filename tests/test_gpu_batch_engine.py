@@ -16,8 +16,6 @@ masks alone.  Here, through `_lib.Batch` itself:
 Every comparison is exact (integers equal, floats equal as uint32 bits).  References: `oracle.trim` with its `Info`, and for what
 the oracle does not report (kept counts, warnings, the row a warning names, the rows of gaps only) a `Context.trim` of the same
 alignment -- the single-alignment path, itself pinned to the oracle by tests/test_gpu_dispatch.py and tests/test_gpu_pipeline.py."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -88,11 +86,8 @@ class Rig:
         """`msa_trim` of one alignment on the context, nothing raised: (keep_res, keep_seq, info, rc, only-gaps rows)"""
         ctx = self.ctx
         ctx.upload(a, indet)
-        m, n = a.shape
-        res, seq, info = np.ones(n, dtype=np.uint8), np.ones(m, dtype=np.uint8), _lib.TrimInfo()
-        rc = ctx.lib.msa_trim(ctx.h, ctypes.byref(p), _lib.ptr(res), _lib.ptr(seq), ctypes.byref(info))
-        ctx._in_flight = None
-        return res.astype(bool), seq.astype(bool), info, rc, ctx.only_gaps_rows() if rc == _lib.OK else []
+        res, seq, info, rc = ctx.trim_rc(p)
+        return res, seq, info, rc, ctx.only_gaps_rows() if rc == _lib.OK else []
 
     def close(self):
         for b in self.made:
